@@ -23,6 +23,13 @@ Rays = primary + secondary + shadow, counted on the device with the same rule
 as the CPU oracle (include/rt_abi.h rt_stats). value = rays of all ranks per
 step / max-over-ranks step time.
 
+A plain run sets up, warms up (--warmup W steps, at least one per frame in
+flight), times --steps K steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line (ms_per_step = wall time of
+the K timed steps / K). The legs that need runs of their own -- the CPU
+baseline, and for C3 the c3cone companion and the rt_render seam leg -- run
+only with --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -51,7 +58,18 @@ def parse():
     p.add_argument("--config", default="c3")
     p.add_argument("--width", type=int, default=None)
     p.add_argument("--height", type=int, default=None)
-    p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run the legs that take runs of their own: the CPU "
+                        "baseline (--cpu-baseline), and for c3 on one GPU the c3cone companion and the "
+                        "rt_render seam leg (--companion). Without it the run sets up, warms up, times the "
+                        "steps and prints the line; those fields are then null or absent")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                        "(rank 0): frame.npy, the RGBA8 frame as float32 (a fixed seeded sample of its rows "
+                        "when the whole frame would pass 64 MB, with their row numbers in frame_rows.npy), "
+                        "and counters.npy, the ray and test counters per timed step as float64")
+    p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                   help="with --full: auto times the CPU oracle on a sample of the same scene")
     p.add_argument("--cpu-threads", type=int, default=8)
     p.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                    help="strong (default): one frame's rows sharded over the ranks + RCCL gather to "
@@ -65,7 +83,7 @@ def parse():
                    help="render only rows [Y0, Y1) of the full-size frame (one GPU): a full-width row "
                         "band of a config too costly to render whole (brute-force C5 at 7680x4320)")
     p.add_argument("--companion", choices=["auto", "off"], default="auto",
-                   help="c3: also time c3cone (C3 with the cone) for the line's c3cone field; "
+                   help="with --full, c3: also time c3cone (C3 with the cone) for the line's c3cone field; "
                         "off in profiling runs, whose counters must come from C3 frames only")
     p.add_argument("--inflight", type=int, default=None,
                    help="frames in flight per rank: F render contexts with the same scene on F streams "
@@ -97,7 +115,10 @@ def parse():
     p.add_argument("--launch-selftest", action="store_true",
                    help="CPU test of the N-rank launch and telemetry path: gloo ranks, synthetic "
                         "per-rank times, no device (tests/test_bench_launch.py)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def inflight_default(args, world):
@@ -276,6 +297,42 @@ def gpu_span_ms(evs):
     frame costs."""
     span = max(evs[0][0].elapsed_time(e1) for _, e1 in evs)
     return span / len(evs)
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all
+DUMP_SEED = 2026
+
+
+def dump_outputs(path, frame, st, steps):
+    """--dump-outputs: what the last timed step handed back on this rank, as
+    .npy files under `path`. frame.npy: the step's RGBA8 frame (the tensor
+    step() / flush() return: the whole frame, or the band of --rows) as float32
+    [rows, W, 4]; when that would pass DUMP_BYTES, a fixed sample of whole rows
+    (a seeded permutation's first rows, ascending), their row numbers in
+    frame_rows.npy. counters.npy (float64): this rank's device counters over
+    the timed steps divided by the step count (every step renders the same
+    frame) -- primary, secondary, shadow rays, shaded hits, surface errors,
+    then the intersection tests and the shadow tests per kind. The scene comes
+    from the arguments alone (configs.py, fixed seeds), so two builds run with
+    the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    counters = np.array([st.primary_rays, st.secondary_rays, st.shadow_rays, st.shaded_hits, st.surface_errors]
+                        + list(st.tests) + list(st.shadow_tests), np.float64) / steps
+    np.save(os.path.join(path, "counters.npy"), counters)
+    img = frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame)  # (--api: a numpy frame)
+    rows = img.shape[0]
+    room = (DUMP_BYTES - counters.nbytes - 1024) // (img.shape[1] * img.shape[2] * 4 + 8)  # a row + its number
+    if rows <= room:
+        if os.path.exists(os.path.join(path, "frame_rows.npy")):  # an earlier, sampled dump's
+            os.remove(os.path.join(path, "frame_rows.npy"))
+    else:
+        if room < 1:
+            raise SystemExit("--dump-outputs: one row of the frame passes %d bytes" % DUMP_BYTES)
+        pick = np.sort(np.random.RandomState(DUMP_SEED).permutation(rows)[:room])
+        np.save(os.path.join(path, "frame_rows.npy"), pick.astype(np.float64))
+        img = img[pick]
+    np.save(os.path.join(path, "frame.npy"), img.astype(np.float32))
 
 
 def make_contexts(pkg, dev, packed, n, specialize, accel=None, schedule="auto", sharing=None):
@@ -469,7 +526,9 @@ def api_main(args):
                      "traffic": None},
         "cpu_baseline": None,
     }
-    if args.cpu_baseline == "auto":
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, st, 1)  # (st: the last call's counters)
+    if args.full and args.cpu_baseline == "auto":
         line["cpu_baseline"] = cpu_baseline(packed, args.cpu_threads)
     print(json.dumps(line), flush=True)
 
@@ -550,7 +609,7 @@ def main():
     t0 = time.perf_counter()
     for k in range(args.steps):
         dr.step(events=evs[k])
-    dr.flush()  # every frame gathered to rank 0 inside the timed region
+    last_frame = dr.flush()  # every frame gathered to rank 0 inside the timed region
     torch.cuda.synchronize()
     barrier()
     t1 = time.perf_counter()
@@ -655,11 +714,15 @@ def main():
         if tb is not None and world == 1 and not args.width and not args.height and not band:
             line["roofline"]["traffic"] = int(tb)
             line["roofline"]["traffic_source"] = src
-        if world == 1 and args.config == "c3" and args.companion == "auto" and not (args.width or args.height or band):
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_frame, st, args.steps)
+        # --full: the legs that take runs of their own
+        companion = args.full and world == 1 and args.config == "c3" and args.companion == "auto" and \
+            not (args.width or args.height or band)
+        if companion:
             line["c3cone"] = side_config(pkg, "c3cone", dev, args.specialize == "on", args.inflight, streams=dr.streams)
-        if world == 1 and args.config == "c3" and args.companion == "auto" and not (args.width or args.height or band):
             line["render_api"] = render_api_leg(pkg, packed)
-        if world == 1 and args.cpu_baseline == "auto":
+        if args.full and world == 1 and args.cpu_baseline == "auto":
             line["cpu_baseline"] = cpu_baseline(packed, args.cpu_threads)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -11,7 +11,7 @@ for c in ${PMC_CFGS:-c3 c3cone c4 c4csg c5}; do
   cp gpurun_out/pmc_$c/pmc_$c.json profiles/pmc_$c.json && cp gpurun_out/pmc_$c/traffic.json profiles/traffic_$c.json || exit 1
 done
 grep -A1 "==" $O/pmc_all.log
-timeout -k 10 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 cat $O/bench_default.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/rocprof -o c3 --output-format csv -- python3 bench.py --steps 30 --warmup 3 --cpu-baseline off --companion off > $O/rocprof_bench.json 2> $O/rocprof_bench.err || { tail -5 $O/rocprof_bench.err; exit 1; }
 python3 scripts/trace_span.py "$(find $O/rocprof -name '*kernel_trace.csv' | head -1)" 30 $O/trace_span_c3.json

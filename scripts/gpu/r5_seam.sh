@@ -10,5 +10,5 @@ timeout -k 10 600 python3 -u -m pytest -x -v --timeout 300 --timeout-method thre
 tail -3 $O/pytest.log
 timeout -k 10 300 python3 scripts/api_seam.py > $O/api_seam.log 2>&1 || { tail -5 $O/api_seam.log; exit 1; }
 cat $O/api_seam.log
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 3 --cpu-baseline off > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 bench.py --steps 20 --warmup 3 --full --cpu-baseline off > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 cat $O/bench.json

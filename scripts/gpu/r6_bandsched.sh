@@ -17,7 +17,7 @@ print('%-10s %.4f ms/call gpu %.3f tail %.3f  first %.1f ms, %d calls to special
   done
 done
 unset RT_PIXEL_QUADS
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --full > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/bench_default.json')); a=d['render_api']
 print('bench', d['ms_per_step'], 'render_api steady', a['steady_ms'], a['parts_ms'], 'calls', a['calls'])"

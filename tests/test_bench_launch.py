@@ -36,6 +36,41 @@ def test_bench_rank_failure_stops_the_launch():
     assert r.returncode != 0
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.py --dump-outputs: float .npy files of at most DUMP_BYTES in all;
+    a frame that fits is written whole, a larger one as a fixed sample of whole
+    rows (the same rows on every run) with their row numbers."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from __graft_entry__ import load_package
+    st = load_package().abi.rt_stats()
+    st.primary_rays, st.secondary_rays, st.shadow_rays = 60, 30, 90
+    st.tests[1] = 120
+
+    def dump(name, img):
+        d = str(tmp_path / name)
+        bench.dump_outputs(d, img, st, 30)
+        files = {n: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))}
+        assert all(v.dtype in (np.float32, np.float64) for v in files.values())
+        assert sum(os.path.getsize(os.path.join(d, n)) for n in files) <= bench.DUMP_BYTES
+        return files
+
+    rng = np.random.RandomState(7)
+    small = rng.randint(0, 256, (45, 37, 4)).astype(np.uint8)
+    f = dump("small", small)
+    assert sorted(f) == ["counters.npy", "frame.npy"]
+    assert np.array_equal(f["frame.npy"], small)
+    assert f["counters.npy"][:3].tolist() == [2.0, 1.0, 3.0] and f["counters.npy"].sum() == 10.0
+
+    big = rng.randint(0, 256, (2160, 3840, 4)).astype(np.uint8)  # 4K: 133 MB as float32
+    f = dump("big", big)
+    rows = f["frame_rows.npy"].astype(np.int64)
+    assert 1000 < len(rows) < 2160 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(f["frame.npy"], big[rows])
+    assert np.array_equal(dump("big_again", big)["frame_rows.npy"], f["frame_rows.npy"])
+
+
 def test_inflight_default():
     """Frames in flight when --inflight is not given: 2, and 3 for the C3
     scenes' strong-scaling shares at >= 4 ranks (bench.inflight_default)."""

@@ -40,7 +40,12 @@ print(lib.rt_debug_getenv(b"RT_ENV_PROBE"), lib.rt_debug_getenv(b"RT_ENV_NEW"), 
 
 
 def test_library_reads_survive_a_thread_rewriting_the_environment():
+    # Every library call releases the GIL (ctypes) and has to take it back from
+    # the churning thread, which gives it up once per switch interval: at the
+    # default 5 ms the 200000 calls wait a quarter of an hour. A short interval
+    # keeps the same number of reads and interleaves the two threads more finely.
     out = _run(r'''
+sys.setswitchinterval(1e-5)
 stop = False
 def churn():
     k = 0

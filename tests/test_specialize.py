@@ -152,7 +152,10 @@ def test_every_kind_of_specialisation_key_compiles():
     assert not bad, bad
 
 
-@pytest.mark.parametrize("key", ["1:0:0", "1:0:0:4:1,3,2,0:15:0:4:6:0:3:0:1", "x:0:0:0::15:0:4:6:0:0:0:1",
+@pytest.mark.parametrize("key", ["1:0:0", "1:0:0:4:1,3,2,0:15:0:4:6:0:3:0:1",
+                                 # (an id of its own: the key's empty field would put "::", the
+                                 # node-id separator, into the test's id)
+                                 pytest.param("x:0:0:0::15:0:4:6:0:0:0:1", id="non-numeric-first-field"),
                                  "1:0:0:9:1:15:0:4:6:0:0:0:1"])
 def test_debug_spec_compile_rejects_malformed_keys(key):
     import ctypes
