@@ -21,6 +21,7 @@ RT_MAX_FACES = 6
 KIND_NAMES = ("sphere", "plane", "cube", "cylinder", "cone", "csg")
 RT_CSG_UNION, RT_CSG_INTERSECT, RT_CSG_DIFFERENCE = -1, -2, -3
 RT_CSG_MAX_LEAVES = 128
+RT_VM_EXT_ASIN, RT_VM_EXT_ACOS, RT_VM_EXT_REAL = 32, 33, 34  # surface bytecode, contest extensions
 RT_SPEC_SURFACES, RT_SPEC_DIRECTIONAL, RT_SPEC_SPOT = 1, 2, 4  # rt_spec_precompile feature bits
 RT_ACCEL_BVH, RT_ACCEL_CULL = 1, 2  # rt_set_accel flags
 RT_SCHED_AUTO, RT_SCHED_PIXEL, RT_SCHED_QUADS, RT_SCHED_PAIRS = 0, 1, 2, 3  # rt_set_schedule modes

@@ -53,7 +53,7 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--extensions", action="store_true",
-                    help="enable cone, light, spotlight, real (ICFP operators the reference lacks)")
+                    help="enable cone, light, spotlight, real, asin, acos, intersect (ICFP operators the reference lacks)")
     a = ap.parse_args(argv)
     if a.out_dir:
         os.makedirs(a.out_dir, exist_ok=True)

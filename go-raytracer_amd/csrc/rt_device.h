@@ -600,6 +600,18 @@ __device__ __forceinline__ double go_satan(double x) {
   if (x > Tan3pio8) return 1.5707963267948966 - go_xatan(1 / x) + Morebits;
   return 0.7853981633974483 + go_xatan((x - 1) / (x + 1)) + 0.5 * Morebits;
 }
+__device__ __forceinline__ double go_asin(double x) {
+  if (x == 0) return x;
+  bool sign = x < 0;
+  double ax = sign ? -x : x;
+  if (ax > 1) return __builtin_nan("");
+  double temp = __builtin_sqrt(1 - ax * ax);
+  temp = (ax > 0.7) ? 1.5707963267948966 - go_satan(temp / ax) : go_satan(ax / temp);
+  return sign ? -temp : temp;
+}
+// (its own copy of Asin's body, as before asin existed here: the generic
+// kernels without the contest extensions stay instruction for instruction
+// what they were, see rt_render_kernel's EXT)
 __device__ __forceinline__ double go_acos(double x) {
   double a;  // Asin(x)
   if (x == 0) {

@@ -84,23 +84,24 @@ __global__ void rt_debug_vm_kernel(const char* __restrict__ blob, int off_code, 
   const uint32_t* code = reinterpret_cast<const uint32_t*>(blob + off_code);
   const uint64_t* consts = reinterpret_cast<const uint64_t*>(blob + off_consts);
   const int* entry = reinterpret_cast<const int*>(blob + off_entry);
-  err[i] = run_vm(code, consts, entry[prog], face[i], u[i], v[i], out + (size_t)i * 10) ? 1 : 0;
+  err[i] = run_vm<true>(code, consts, entry[prog], face[i], u[i], v[i], out + (size_t)i * 10) ? 1 : 0;
 }
 
-// The ahead-of-time flavours: <scene in LDS, BVH, CSG, pixel quads>, indexed
-// by kernel_index(); launch() picks one per scene.
-constexpr int kernel_index(bool lds, bool bvh, bool csg, bool quads) {
-  return (lds ? 1 : 0) | (bvh ? 2 : 0) | (csg ? 4 : 0) | (quads ? 8 : 0);
+// The ahead-of-time flavours: <scene in LDS, BVH, CSG, pixel quads, contest
+// extension code (rt_render.h EXT)>, indexed by kernel_index(); launch() picks
+// one per scene.
+constexpr int kernel_index(bool lds, bool bvh, bool csg, bool quads, bool ext) {
+  return (lds ? 1 : 0) | (bvh ? 2 : 0) | (csg ? 4 : 0) | (quads ? 8 : 0) | (ext ? 16 : 0);
 }
 template <int I>
 constexpr const void* kernel_at() {
-  return (const void*)rt_render_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0>;
+  return (const void*)rt_render_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0, (I & 16) != 0>;
 }
 template <int... I>
 constexpr std::array<const void*, sizeof...(I)> kernel_table(std::integer_sequence<int, I...>) {
   return {kernel_at<I>()...};
 }
-const std::array<const void*, 16> k_kernels = kernel_table(std::make_integer_sequence<int, 16>{});
+const std::array<const void*, 32> k_kernels = kernel_table(std::make_integer_sequence<int, 32>{});
 // ===========================================================================
 // Host side: scene conversion (raytracer.go:724-830) and the C ABI
 // ===========================================================================
@@ -301,6 +302,7 @@ struct DevScene {
   int light_mask = 0;  // bit k: the scene has lights of kind k (RT_LIGHT_*)
   bool branching = false;  // some material is reflective and transparent, or a surface program may make one
   int leaf_kind_mask = 0;  // bit k: some CSG leaf has kind k
+  bool ext_code = false;   // a cone leaf or an RT_VM_EXT_* opcode: the kernels built with EXT
   size_t off_nodes = 0, off_bobj = 0, off_planes = 0, off_runs = 0, off_arec = 0, off_urec = 0;
   double bvh_lo[3] = {0, 0, 0}, bvh_hi[3] = {0, 0, 0};  // padded box of the BVH objects (far_shift)
   int nruns = 0;
@@ -1513,12 +1515,12 @@ int rt_create(int device, rt_context** out) {
   // Persistent grids: as many workgroups as are resident (any extra block just
   // finds the queue drained). The LDS flavour is sized for the LDS budget.
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_kernels[kernel_index(true, false, false, false)], WG, LDS_MAX_BYTES) !=
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_kernels[kernel_index(true, false, false, false, false)], WG, LDS_MAX_BYTES) !=
           hipSuccess || per_cu <= 0)
     per_cu = 2;
   c->grid_lds = c->cus * std::min(per_cu, 8);
   per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_kernels[kernel_index(false, false, false, false)], WG, 0) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_kernels[kernel_index(false, false, false, false, false)], WG, 0) != hipSuccess ||
       per_cu <= 0)
     per_cu = 2;
   c->grid_glb = c->cus * std::min(per_cu, 8);
@@ -1638,8 +1640,9 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
     const bool leaf = i >= s.nobj;
     const rt_object& o = leaf ? in->csg_leaves[i - s.nobj] : in->objects[i];
     if (o.kind < 0 || o.kind >= RT_NUM_KINDS) return fail(RT_E_INVALID, "unknown scene object type");
-    if (leaf && o.kind != RT_SPHERE && o.kind != RT_CUBE && o.kind != RT_CYLINDER && o.kind != RT_PLANE)
-      return fail(RT_E_INVALID, "CSG leaves are spheres, cubes, cylinders or planes");
+    if (leaf && o.kind != RT_SPHERE && o.kind != RT_CUBE && o.kind != RT_CYLINDER && o.kind != RT_PLANE &&
+        o.kind != RT_CONE)
+      return fail(RT_E_INVALID, "CSG leaves are spheres, cubes, cylinders, cones or planes");
     kind[i] = o.kind;
     if (o.kind == RT_CSG) {  // validated program; geometry filled in below
       if (o.csg_count <= 0 || o.csg_count > RT_CSG_MAX_LEAVES || o.csg_first < 0 ||
@@ -1988,9 +1991,10 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
       for (int steps = 0; steps < VM_MAX_STEPS && pc + 1 < ncode; steps++, pc += 2) {
         uint32_t w0 = in->program_code[pc], cc = in->program_code[pc + 1];
         int op = (int)(w0 & 0xff);
-        if (op > VM_RET || ((w0 >> 8) & 0xff) >= VM_REGS || ((w0 >> 16) & 0xff) >= VM_REGS ||
+        if (op > VM_LAST || ((w0 >> 8) & 0xff) >= VM_REGS || ((w0 >> 16) & 0xff) >= VM_REGS ||
             (w0 >> 24) >= VM_REGS)
           return fail(RT_E_INVALID, "surface program: bad opcode or register");
+        if (op > VM_RET) s.ext_code = true;
         if (op == VM_CONST && cc >= (uint32_t)nconst) return fail(RT_E_INVALID, "surface program: bad constant");
         if (op == VM_TBL) {
           if (cc >= (uint32_t)nconst) return fail(RT_E_INVALID, "surface program: bad table");
@@ -2064,6 +2068,7 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
     }
     for (int i = 0; i < s.nobj; i++) s.kind_mask |= 1 << kind[i];
     for (int i = s.nobj; i < ntot; i++) s.leaf_kind_mask |= 1 << kind[i];
+    if ((s.leaf_kind_mask >> RT_CONE) & 1) s.ext_code = true;
     s.off_nodes = 0;
     s.off_bobj = (b.nodes.size() * sizeof(float) + 15) & ~(size_t)15;
     s.off_planes = s.off_bobj + ((b.leaf_geo.size() * sizeof(double) + 15) & ~(size_t)15);
@@ -2340,7 +2345,7 @@ static int launch(rt_context* c, int y0, int y1, int trow0, int stride, int ntro
   const bool use_stream = !lds && !s.use_bvh && !s.has_csg && (spec_extra || !(spec && !(c->accel & RT_ACCEL_CULL)));
   // the generic kernels have no pairs flavour: quads instead (same pixels)
   const bool quads = sch == SCH_QUADS || (sch == SCH_PAIRS && !spec);
-  const void* kfn = k_kernels[kernel_index(lds, s.use_bvh, s.has_csg, quads)];
+  const void* kfn = k_kernels[kernel_index(lds, s.use_bvh, s.has_csg, quads, s.ext_code)];
   // the board is in LDS only for a kernel compiled with work sharing
   const bool share = spec && share_m == RT_SHARE_GROUP;  // (the device-wide board is in HBM)
   const int stream_off = board_off + (share ? BOARD_BYTES : 0);

@@ -898,8 +898,9 @@ __device__ __forceinline__ F3 f3_rcp(F3 d) {
 // ---- CSG composites (contest extension; oracle/rt_oracle.c leaf_interval,
 // csg_member, csg_intersect restate the same semantics op for op) ----
 // One convex leaf's interval [a, b] along the ray and the faces it enters /
-// leaves by: f = fa | fb << 4 | 256 when non-empty.
-template <typename DP>
+// leaves by: f = fa | fb << 4 | 256 when non-empty. CL: built with the cone
+// leaf (see rt_render_kernel's EXT).
+template <bool CL, typename DP>
 __device__ __forceinline__ void leaf_interval(int kind, DP g, const Ray& r, double& a, double& b, int& f) {
   const Ray l = to_obj(g, r);
   a = -__builtin_inf();
@@ -984,6 +985,49 @@ __device__ __forceinline__ void leaf_interval(int kind, DP g, const Ray& r, doub
       }
       if (a > b) ok = false;
     }
+  } else if (CL && spec_kind(RT_CONE) && kind == RT_CONE) {
+    // The cone's interval spans exactly the candidates quadric_hit_c forms
+    // for a cone (side roots, generator-parallel root, base), op for op but
+    // without the t > 0 filter: a composite that is one cone hits at the
+    // plain cone's t and face, bit for bit. First candidate wins a tie.
+    double qa = l.d.x * l.d.x + l.d.z * l.d.z, hb = l.o.x * l.d.x + l.o.z * l.d.z;
+    qa = qa - l.d.y * l.d.y;
+    hb = hb - l.o.y * l.d.y;
+    const double c0 = quadric_c0(l.o, true);
+    a = __builtin_inf();  // no valid candidate yet
+    b = -__builtin_inf();
+    auto side = [&](double t) {
+      const double y = l.o.y + l.d.y * t;
+      if (y >= 0.0 && y <= 1.0) {
+        if (t < a) a = t;
+        if (t > b) b = t;
+      }
+    };
+    if (__builtin_fabs(qa) > 1e-12) {
+      const double disc = hb * hb - qa * c0;
+      if (disc >= 0.0) {
+        const double sq = gsqrt(disc);
+        side((-hb - sq) / qa);
+        side((-hb + sq) / qa);
+      }
+    } else if (__builtin_fabs(hb) > 1e-12) {
+      side(-c0 / (2.0 * hb));
+    }
+    if (__builtin_fabs(l.d.y) > 1e-12) {
+      const double tt = (1.0 - l.o.y) / l.d.y;
+      const double px = l.o.x + l.d.x * tt, pz = l.o.z + l.d.z * tt;
+      if (px * px + pz * pz <= 1.0) {
+        if (tt < a) {
+          a = tt;
+          fa = 1;
+        }
+        if (tt > b) {
+          b = tt;
+          fb = 1;
+        }
+      }
+    }
+    if (a > b) ok = false;  // no valid candidate: empty (one: a == b, zero length)
   } else {  // RT_PLANE: the half-space n.p + D <= 0
     const d3 n = mk(g[12], g[13], g[14]);
     const double denom = dot(n, l.d);
@@ -1060,7 +1104,7 @@ __device__ __forceinline__ bool csg_eval(IP code, int n, uint64_t m0, uint64_t m
 // (strictly beyond, or at-or-beyond when !cut_strict): the caller cannot use
 // such a hit (closest hit: t > best; shadow: t * |d| >= dist), so stopping
 // there changes no result.
-template <typename DP, typename IP, typename GP>
+template <bool CL, typename DP, typename IP, typename GP>
 __device__ __forceinline__ bool csg_hit_all(DP geo, IP kinds, IP code, int nobj,
                                             GP g, const Ray& r, double& t, int& face, double cut_m,
                                             double cut_lim, bool cut_strict) {
@@ -1080,7 +1124,7 @@ __device__ __forceinline__ bool csg_hit_all(DP geo, IP kinds, IP code, int nobj,
     const int k = kinds[first + j];
     const auto lg = geo + (size_t)(first + j) * GEO;
     if (k != RT_PLANE && !may_hit(of, df, 3.0e38f, lg, slack)) continue;
-    leaf_interval(k, lg, r, A[j], B[j], F[j]);
+    leaf_interval<CL>(k, lg, r, A[j], B[j], F[j]);
     if (F[j] & 256) {
       if (j < 64)
         live0 |= 1ull << j;
@@ -1155,11 +1199,11 @@ __device__ unsigned long long g_csg_diag[8];  // diagnostic build: searches, ove
 #ifndef RT_CSG_LIVE
 #define RT_CSG_LIVE 6  // 0: always the scratch-array search
 #endif
-template <typename DP, typename IP, typename GP>
+template <bool CL, typename DP, typename IP, typename GP>
 __device__ __forceinline__ bool csg_hit_all_call(DP geo, IP kinds, IP code, int nobj,
                                               GP g, const Ray& r, double& t, int& face, double cut_m,
                                               double cut_lim, bool cut_strict) {
-  return csg_hit_all(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
+  return csg_hit_all<CL>(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
 }
 // Callers pass a WAVE-UNIFORM composite g (every lane searches the same
 // composite): its fields are read through readfirstlane below. That holds
@@ -1169,12 +1213,12 @@ __device__ __forceinline__ bool csg_hit_all_call(DP geo, IP kinds, IP code, int 
 // LF packs the leaf number in 8 bits (and the host's leaf groups use 0xff as
 // the end marker), hence:
 static_assert(RT_CSG_MAX_LEAVES < 255, "csg_hit packs leaf numbers in 8 bits");
-template <typename DP, typename IP, typename GP>
+template <bool CL, typename DP, typename IP, typename GP>
 __device__ __forceinline__ bool csg_hit(DP geo, IP kinds, IP code, int nobj,
                                         GP g, const Ray& r, double& t, int& face, double cut_m = 1.0,
                                         double cut_lim = __builtin_inf(), bool cut_strict = true) {
   constexpr int K = RT_CSG_LIVE > 0 ? RT_CSG_LIVE : 1;
-  if constexpr (RT_CSG_LIVE == 0) return csg_hit_all(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
+  if constexpr (RT_CSG_LIVE == 0) return csg_hit_all<CL>(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
   const auto ci = as_i(g + 14);
   // (the composite's fields are wave-uniform: readfirstlane keeps the reads
   // below them scalar)
@@ -1222,7 +1266,7 @@ __device__ __forceinline__ bool csg_hit(DP geo, IP kinds, IP code, int nobj,
     if (k != RT_PLANE && !may_hit(of, df, 3.0e38f, lg, slack)) return;
     double a, b;
     int f;
-    leaf_interval(k, lg, r, a, b, f);
+    leaf_interval<CL>(k, lg, r, a, b, f);
     if (f & 256) {
 #pragma unroll
       for (int s = 0; s < K; s++)
@@ -1287,7 +1331,7 @@ __device__ __forceinline__ bool csg_hit(DP geo, IP kinds, IP code, int nobj,
   if (n > K) atomicAdd(RT_CSG_DIAG + 1, 1ull);  // ... that overflowed the register list
   atomicAdd(RT_CSG_DIAG + 2, (unsigned long long)n);  // live leaves
 #endif
-  if (n > K) return csg_hit_all_call(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
+  if (n > K) return csg_hit_all_call<CL>(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
   for (;;) {
     double te = __builtin_inf();
     int se = -1, jend = 0, je = 0x7fffffff;
@@ -1699,16 +1743,22 @@ __device__ __forceinline__ void gs_deliver(uint64_t* board, int q, d3 c) {
 enum VmOp {
   VM_NOP, VM_CONST, VM_MOV, VM_ADDF, VM_SUBF, VM_MULF, VM_DIVF, VM_NEGF, VM_ADDI, VM_SUBI, VM_MULI, VM_DIVI,
   VM_MODI, VM_NEGI, VM_LTF, VM_EQF, VM_LTI, VM_EQI, VM_SEL, VM_FLOOR, VM_FRAC, VM_SQRT, VM_SIN, VM_COS,
-  VM_CLAMPF, VM_CLAMPI, VM_TBL, VM_AND, VM_OR, VM_NOT, VM_ERR, VM_RET
+  VM_CLAMPF, VM_CLAMPI, VM_TBL, VM_AND, VM_OR, VM_NOT, VM_ERR, VM_RET,
+  // contest extensions (GML `asin`, `acos`, `real`): degrees out, 57.29577951308232 * Go math.Asin / Acos
+  VM_EXT_ASIN, VM_EXT_ACOS, VM_EXT_REAL,
+  VM_LAST = VM_EXT_REAL
 };
 enum { VM_REGS = 64, VM_MAX_STEPS = 8192 };
 static_assert(VM_CONST == RT_VM_CONST && VM_SEL == RT_VM_SEL && VM_TBL == RT_VM_TBL && VM_ERR == RT_VM_ERR &&
-                  VM_RET == RT_VM_RET,
+                  VM_RET == RT_VM_RET && VM_EXT_ASIN == RT_VM_EXT_ASIN && VM_EXT_ACOS == RT_VM_EXT_ACOS &&
+                  VM_EXT_REAL == RT_VM_EXT_REAL,
               "surface bytecode opcodes of include/rt_abi.h");
 
 // Inlined: as an out-of-line call reading the LDS-staged program through
 // generic pointers it rendered wrong pixels on gfx950 (measured: the global
 // blob path and the inlined call are exact), and inlining needs less scratch.
+// EXT: with the contest-extension opcodes (see rt_render_kernel).
+template <bool EXT>
 __device__ __forceinline__ bool run_vm(const uint32_t* code, const uint64_t* consts, int pc, long long face, double u,
                                     double v, double* out) {
   uint64_t R[VM_REGS];
@@ -1786,7 +1836,28 @@ __device__ __forceinline__ bool run_vm(const uint32_t* code, const uint64_t* con
       case VM_OR: R[d] = (R[a] != 0) || (R[b] != 0); break;
       case VM_NOT: R[d] = R[a] == 0; break;
       case VM_ERR: err = err || (R[a] != 0); break;
-      default: return true;
+      default:
+        if constexpr (EXT) {
+          // asin / acos: a NaN operand comes out as it went in, which is what
+          // Go's chain of amd64 operations makes of it (the sign a device
+          // subtraction would give it is not); |x| > 1: NaN, not Pi/2 - NaN
+          if (op == VM_EXT_ASIN || op == VM_EXT_ACOS) {
+            const double x = F_(a);
+            double r = x;
+            if (x == x) {
+              r = go_asin(x);
+              if (op == VM_EXT_ACOS) r = __builtin_fabs(x) > 1 ? __builtin_nan("") : 1.5707963267948966 - r;
+              r = 57.29577951308232 * r;
+            }
+            SETF(r);
+            break;
+          }
+          if (op == VM_EXT_REAL) {
+            SETF((double)I_(a));
+            break;
+          }
+        }
+        return true;
     }
   }
 #undef F_
@@ -1819,7 +1890,17 @@ struct View {
 // not one after another in one lane -- 4x shorter per-pixel latency, so the
 // deep, branching trees of glass at depth >= 7 no longer leave a few waves
 // running long after the rest (host choice per scene, rt_kernel.hip).
-template <bool LDS, bool BVH, bool CSG, bool QUADS>
+// EXT: with the code of the later contest extensions, cone leaves in the
+// composite search and the asin / acos / real opcodes of the VM. The generic
+// kernels are register-bound (the CSG ones spill 160 VGPRs), and any code
+// added to them moves the spills and the frame time by up to 1 % (c4csg
+// generic: 10.89 -> 10.97 ms with the cone branch and the opcodes, 11.08 with
+// the cone branch alone; profiles/r07/cone_leaf/). So the ahead-of-time
+// kernels come without it, instruction for instruction what they were, and
+// with it; launch() takes the second set only for a scene that has a cone
+// leaf or an extension opcode. Specialised builds name four arguments: there
+// spec_kind / spec_feat fold away what the scene lacks.
+template <bool LDS, bool BVH, bool CSG, bool QUADS, bool EXT = true>
 #ifndef RT_MIN_WAVES
 #if RT_CULL
 #define RT_MIN_WAVES 3  // 168 VGPRs -> 3 waves/SIMD (C3 on par with 4; C2 -10%, C4 (BVH) -4%)
@@ -2927,7 +3008,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
           int f;
           bool h;
           if constexpr (CSG)
-            h = k == RT_CSG ? csg_hit(CSG_ARGS, P.nobj, CSG_G(i, g), ray, t, f, 1.0,
+            h = k == RT_CSG ? csg_hit<EXT>(CSG_ARGS, P.nobj, CSG_G(i, g), ray, t, f, 1.0,
                                       found ? best_t : __builtin_inf(), true)
                             : object_hit(k, g, ray, t, f);
           else
@@ -3253,7 +3334,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
           v = p.z;
         }
         double r[10];
-        bad = run_vm(S.code, S.consts, S.entry[-mat - 1], face, u, v, r) || bad;
+        bad = run_vm<EXT>(S.code, S.consts, S.entry[-mat - 1], face, u, v, r) || bad;
         if (bad)  // counted; the material reads as all-zero (oracle convention)
           for (int k = 0; k < 10; k++) r[k] = 0.0;
         vmrec[0] = r[0];
@@ -3603,7 +3684,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
             int f;
             bool h;
             if constexpr (CSG)
-              h = k == RT_CSG ? csg_hit(CSG_ARGS, P.nobj, CSG_G(i, g), sr, t, f, rlen, dist, false)
+              h = k == RT_CSG ? csg_hit<EXT>(CSG_ARGS, P.nobj, CSG_G(i, g), sr, t, f, rlen, dist, false)
                               : object_hit(k, g, sr, t, f);
             else
               h = object_hit(k, g, sr, t, f);
@@ -3629,7 +3710,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
             int f;
             bool h;
             if constexpr (CSG)
-              h = k == RT_CSG ? csg_hit(CSG_ARGS, P.nobj, CSG_G(i, g), sr, t, f, rlen, dist, false)
+              h = k == RT_CSG ? csg_hit<EXT>(CSG_ARGS, P.nobj, CSG_G(i, g), sr, t, f, rlen, dist, false)
                               : object_hit(k, g, sr, t, f);
             else
               h = object_hit(k, g, sr, t, f);

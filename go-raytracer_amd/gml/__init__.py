@@ -19,7 +19,8 @@ def _hook(out):
 def run_file(path, extensions=False):
     """Evaluate a .gml file; returns the list of (RenderArgs, EvalState) it
     rendered (in order) and the final EvalState. extensions=True enables the
-    ICFP operators the reference lacks (cone, light, spotlight, real)."""
+    ICFP operators the reference lacks (cone, light, spotlight, real, asin,
+    acos, intersect)."""
     out = []
     st = EvalState(render=_hook(out), extensions=extensions)
     st.parse_and_eval_file(path)

@@ -148,8 +148,8 @@ class EvalState:
         self.render = render
         self.cur = None
         # ICFP 2000 operators the reference lacks (cone, light, spotlight,
-        # real): off by default, so programs behave exactly as in the reference
-        # ("unbound identifier" for these names).
+        # real, asin, acos, intersect): off by default, so programs behave
+        # exactly as in the reference ("unbound identifier" for these names).
         self.extensions = extensions
 
     # -- program entry points (evaluator.go:305-356) --
@@ -168,8 +168,37 @@ class EvalState:
         return c
 
     def eval(self, program):
-        for tok in program:
-            self.step(tok)
+        """Run a token list. `apply` and `if` bodies run on an explicit frame
+        stack here rather than by recursion: GML loops are recursive closures
+        (a `foreach` over 25 000 elements is 25 000 applies deep), far beyond
+        the host's call stack. A frame is [code, next index, environment to
+        restore when the body ends] (EvalClosure's save / restore)."""
+        frames = [[program, 0, None]]
+        try:
+            while frames:
+                fr = frames[-1]
+                code, i = fr[0], fr[1]
+                if i == len(code):
+                    frames.pop()
+                    if fr[2] is not None:
+                        self.env = fr[2]
+                    continue
+                fr[1] = i + 1
+                tok = code[i]
+                if type(tok) is X.Identifier and (tok.name == "apply" or tok.name == "if"):
+                    # (builtin names cannot be rebound: the lookup order of step)
+                    self.cur = tok
+                    c = _closure(self) if tok.name == "apply" else _if_branch(self)
+                    frames.append([c.code, 0, self.env])
+                    self.env = dict(c.env)
+                else:
+                    self.step(tok)
+        except BaseException:
+            for fr in frames:  # as the nested EvalClosure calls would unwind: the outermost caller's
+                if fr[2] is not None:
+                    self.env = fr[2]
+                    break
+            raise
 
     def step(self, tok):
         """EvalOneStep (evaluator.go:365-414)."""
@@ -438,10 +467,15 @@ def b_get(e):
     e.stack.append(arr.elements[i])
 
 
-def b_if(e):
+def _if_branch(e):
+    """The closure `cond tc fc if` runs."""
     tc, fc = _pop2(e, _closure)
     cond = e.pop_t(VBool, "gml.VBool")
-    e.eval_closure(tc if cond.v else fc)
+    return tc if cond.v else fc
+
+
+def b_if(e):
+    e.eval_closure(_if_branch(e))
 
 
 def _xform(mk):
@@ -632,5 +666,17 @@ def b_intersect(e):
     e.stack.append(S.Intersect(a, b))
 
 
+RAD_TO_DEG = 57.29577951308232  # 180 / Pi, rounded once (DEG_TO_RAD's counterpart)
+
+
+def b_asin(e):
+    """`x asin`: degrees, one product like `sin`; NaN for |x| > 1 (Go math.Asin)."""
+    e.stack.append(VReal(RAD_TO_DEG * gomath.go_asin(float(_real(e)))))
+
+
+def b_acos(e):
+    e.stack.append(VReal(RAD_TO_DEG * gomath.go_acos(float(_real(e)))))
+
+
 EXT_BUILTINS = {"cone": b_cone, "light": b_light, "spotlight": b_spotlight, "real": b_real,
-                "intersect": b_intersect}
+                "intersect": b_intersect, "asin": b_asin, "acos": b_acos}

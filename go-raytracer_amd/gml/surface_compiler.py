@@ -17,21 +17,27 @@ Bytecode (include/rt_abi.h, rt_program_set): instruction = 2 x uint32,
   w0 = op | dst << 8 | a << 16 | b << 24,   w1 = c (third operand / constant index)
 registers are 64-bit (f64, i64 or bool 0/1); r0..r9 = the result Material
 (colour xyz, reflectivity, fuzziness, transparency, refractive index, kd, ks,
-n); r10 = face (i64), r11 = u, r12 = v; temporaries from r13.
+n); r10 = face (i64), r11 = u, r12 = v; temporaries from r13. Every value gets
+a register of its own; a program that outgrows the 64 registers that way is
+renumbered with reuse of dead registers (allocate_registers). Programs
+evaluated with the contest extensions may also use asin, acos and real
+(EXT_OPS, include/rt_abi.h RT_VM_EXT_*).
 """
 import math
 
 from .. import scene as S
 from . import syntax as X
-from .evaluator import (BUILTINS, VArray, VBool, VClosure, VInt, VReal, Vec3, _fdiv, go_f2i, wrap64,
-                        DEG_TO_RAD)
+from .evaluator import (BUILTINS, EXT_BUILTINS, VArray, VBool, VClosure, VInt, VReal, Vec3, _fdiv, go_f2i, wrap64,
+                        DEG_TO_RAD, RAD_TO_DEG)
 from .. import gomath
 
 # opcodes (keep in sync with csrc/rt_kernel.hip enum VmOp)
 OPS = ["NOP", "CONST", "MOV", "ADDF", "SUBF", "MULF", "DIVF", "NEGF", "ADDI", "SUBI", "MULI", "DIVI", "MODI",
        "NEGI", "LTF", "EQF", "LTI", "EQI", "SEL", "FLOOR", "FRAC", "SQRT", "SIN", "COS", "CLAMPF", "CLAMPI",
        "TBL", "AND", "OR", "NOT", "ERR", "RET"]
-OP = {n: i for i, n in enumerate(OPS)}
+# contest-extension opcodes (include/rt_abi.h RT_VM_EXT_*): numbered after the base table
+EXT_OPS = ["ASIN", "ACOS", "REAL"]
+OP = {n: i for i, n in enumerate(OPS + EXT_OPS)}
 R_OUT = 0
 R_FACE, R_U, R_V = 10, 11, 12
 R_FIRST_TEMP = 13
@@ -123,7 +129,8 @@ class Program:
 
 
 class Compiler:
-    def __init__(self, base_stack):
+    def __init__(self, base_stack, extensions=False):
+        self.extensions = extensions  # the program was evaluated with the contest operators
         self.p = Program()
         self.stack = list(base_stack)
         self.base = list(base_stack)
@@ -133,8 +140,7 @@ class Compiler:
 
     # ---- emission ----
     def _reg(self, t):
-        if self.p.nreg >= MAX_REGS:
-            raise CompileError("surface function needs more than %d registers" % MAX_REGS)
+        # (virtual numbers: result() renumbers a program that outgrows the file)
         r = Reg(self.p.nreg, t)
         self.p.nreg += 1
         return r
@@ -262,7 +268,7 @@ class Compiler:
         elif t is X.Binder:
             self.env[tok.id] = self.pop()
         elif t is X.Identifier:
-            if tok.name in BUILTINS:
+            if tok.name in BUILTINS or (self.extensions and tok.name in EXT_BUILTINS):
                 fn = getattr(self, "b_" + tok.name, None)
                 if fn is None:
                     raise CompileError("builtin %s is not supported in device surface functions" % tok.name)
@@ -398,6 +404,16 @@ class Compiler:
 
     def b_cos(self):
         self._funary("COS", lambda x: VReal(gomath.go_cos(DEG_TO_RAD * x)))
+
+    def b_asin(self):
+        self._funary("ASIN", lambda x: VReal(RAD_TO_DEG * gomath.go_asin(x)))
+
+    def b_acos(self):
+        self._funary("ACOS", lambda x: VReal(RAD_TO_DEG * gomath.go_acos(x)))
+
+    def b_real(self):
+        a = self.pop_int()
+        self.push(VReal(float(int(a))) if not isinstance(a, Reg) else self.emit("REAL", "f", a.r))
 
     def b_clampf(self):
         def f(x):
@@ -586,6 +602,8 @@ class Compiler:
         for k, v in enumerate(outs):
             self.emit("MOV", "f", self.freg(v).r, dst=Reg(R_OUT + k, "f"))
         self.emit("RET", "f", dst=Reg(0, "f"))
+        if self.p.nreg > MAX_REGS:
+            allocate_registers(self.p)
         return self.p
 
 
@@ -642,10 +660,92 @@ def _b_get(self):
 Compiler.b_get = _b_get
 
 
-def compile_surface(sf, state_stack=()):
+# ---- register reuse ----
+# Which operand fields of an instruction are registers it reads (the rest of
+# the opcodes read a and b); ERR, RET and NOP write no register.
+_READS = {"NOP": "", "CONST": "", "RET": "", "SEL": "abc"}
+_READS.update({n: "a" for n in ("MOV", "NEGF", "NEGI", "FLOOR", "FRAC", "SQRT", "SIN", "COS", "CLAMPF", "CLAMPI",
+                                "TBL", "NOT", "ERR", "ASIN", "ACOS", "REAL")})
+_NO_WRITE = ("NOP", "ERR", "RET")
+
+
+def allocate_registers(p):
+    """Renumber the temporaries (r13 and up) of a program that needs more than
+    MAX_REGS registers as first numbered. Programs are straight-line and every
+    temporary is written once, so liveness is one backward scan (the last
+    read); a forward pass then hands each new value the lowest register whose
+    value is dead. When none is free, the constant with the most distant next
+    read gives up its register and is loaded again (a second CONST) before
+    that read. CompileError when the values live at once still exceed the file."""
+    names = OPS + EXT_OPS
+    code = p.code
+    uses = {}  # temporary -> positions that read it, ascending
+    for i, (op, d, a, b, c) in enumerate(code):
+        f = {"a": a, "b": b, "c": c}
+        for v in {f[k] for k in _READS.get(names[op], "ab") if f[k] >= R_FIRST_TEMP}:
+            uses.setdefault(v, []).append(i)
+    const_of = {d: c for op, d, a, b, c in code if op == OP["CONST"] and d >= R_FIRST_TEMP}
+    free = list(range(MAX_REGS - 1, R_FIRST_TEMP - 1, -1))  # pop() yields the lowest
+    where = {}  # temporary -> its register, while resident
+    nxt = {v: 0 for v in uses}  # index into uses[v] of the next read
+    out = []
+    top = R_FIRST_TEMP
+
+    def take(i, keep):
+        nonlocal top
+        if not free:
+            # evict the resident constant read again latest (not one this instruction needs)
+            best, far = None, -1
+            for v, r in where.items():
+                if v in const_of and v not in keep:
+                    u = uses[v][nxt[v]] if v in uses and nxt[v] < len(uses[v]) else len(code)
+                    if u > far:
+                        best, far = v, u
+            if best is None:
+                raise CompileError("surface function needs more than %d registers" % MAX_REGS)
+            free.append(where.pop(best))
+        r = free.pop()
+        top = max(top, r + 1)
+        return r
+
+    for i, (op, d, a, b, c) in enumerate(code):
+        name = names[op]
+        f = {"a": a, "b": b, "c": c}
+        rd = [k for k in _READS.get(name, "ab") if f[k] >= R_FIRST_TEMP]
+        keep = {f[k] for k in rd}
+        for k in rd:  # a constant that lost its register: load it again
+            v = f[k]
+            if v not in where:
+                where[v] = take(i, keep)
+                out.append((OP["CONST"], where[v], 0, 0, const_of[v]))
+        g = {k: (where[f[k]] if k in rd else f[k]) for k in "abc"}
+        for v in keep:  # the value dies at its last read: the result may take its register
+            nxt[v] += 1
+            if nxt[v] == len(uses[v]):
+                free.append(where.pop(v))
+                free.sort(reverse=True)
+        if name not in _NO_WRITE and d >= R_FIRST_TEMP:
+            if d not in uses:  # never read: no register to hold
+                if name != "CONST":
+                    out.append((op, take(i, ()), g["a"], g["b"], g["c"]))
+                    free.append(out[-1][1])
+                    free.sort(reverse=True)
+                continue
+            where[d] = take(i, ())
+            out.append((op, where[d], g["a"], g["b"], g["c"]))
+        else:
+            out.append((op, d, g["a"], g["b"], g["c"]))
+    if len(out) > MAX_INSTRS:
+        raise CompileError("surface function too large for the device VM")
+    p.code = out
+    p.nreg = top
+
+
+def compile_surface(sf, state_stack=(), extensions=False):
     """SurfaceFn (closure) -> Program. `state_stack`: the EvalState stack at
-    render time (the per-thread clone EvalSurfaceFn pushes onto)."""
-    c = Compiler(state_stack)
+    render time (the per-thread clone EvalSurfaceFn pushes onto); `extensions`:
+    whether the program ran with the contest operators (asin, acos, real)."""
+    c = Compiler(state_stack, extensions)
     c.push(Reg(R_FACE, "i"))
     c.push(Reg(R_U, "f"))
     c.push(Reg(R_V, "f"))

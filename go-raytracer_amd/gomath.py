@@ -6,7 +6,8 @@ host-side scene builder for transforms (internal/prim/vec.go:258-268,
 376-425) -- the same values the reference's GML evaluator produces.
 
 Third-party algorithms (Go standard library, go 1.24.5 per go.mod:3):
-math.Sin / math.Cos (sin.go, Cephes with Cody-Waite reduction).
+math.Sin / math.Cos (sin.go, Cephes with Cody-Waite reduction); math.Asin /
+math.Acos (asin.go over atan.go's satan / xatan, Cephes).
 """
 import math
 
@@ -91,6 +92,56 @@ def go_cos(x):
     else:
         y = _poly_cos(zz)
     return -y if sign else y
+
+
+# ---- math.Asin / math.Acos (Go asin.go over atan.go's satan, Cephes) --------
+
+_ATAN_P = (-8.750608600031904122785e-01, -1.615753718733365076637e+01, -7.500855792314704667340e+01,
+           -1.228866684490136173410e+02, -6.485021904942025371773e+01)
+_ATAN_Q = (+2.485846490142306297962e+01, +1.650270098316988542046e+02, +4.328810604912902668951e+02,
+           +4.853903996359136964868e+02, +1.945506571482613964425e+02)
+PI_2 = 1.5707963267948966  # Go const Pi/2, rounded once
+PI_4 = 0.7853981633974483
+_MOREBITS = 6.123233995736765886130e-17
+_TAN3PIO8 = 2.41421356237309504880
+
+
+def _xatan(x):
+    P, Q = _ATAN_P, _ATAN_Q
+    z = x * x
+    z = z * ((((P[0] * z + P[1]) * z + P[2]) * z + P[3]) * z + P[4]) / (((((z + Q[0]) * z + Q[1]) * z + Q[2]) * z + Q[3]) * z + Q[4])
+    return x * z + x
+
+
+def _satan(x):
+    if x <= 0.66:
+        return _xatan(x)
+    if x > _TAN3PIO8:
+        return PI_2 - _xatan(1 / x) + _MOREBITS
+    return PI_4 + _xatan((x - 1) / (x + 1)) + 0.5 * _MOREBITS
+
+
+def go_asin(x):
+    """math.Asin (asin.go): NaN for |x| > 1."""
+    if x == 0:
+        return x
+    sign = False
+    if x < 0:
+        x = -x
+        sign = True
+    if x > 1:
+        return math.nan
+    temp = math.sqrt(1 - x * x)
+    if x > 0.7:
+        temp = PI_2 - _satan(temp / x)
+    else:
+        temp = _satan(x / temp)  # (temp >= 0.71 here, or NaN)
+    return -temp if sign else temp
+
+
+def go_acos(x):
+    """math.Acos (asin.go): Pi/2 - Asin(x)."""
+    return PI_2 - go_asin(x)
 
 
 # ---- prim.Mat4 (internal/prim/vec.go:256-425) -----------------------------

@@ -220,7 +220,7 @@ def flatten(root):
     return out
 
 
-_CSG_LEAF = (Sphere, Cube, Cylinder, Plane)
+_CSG_LEAF = (Sphere, Cube, Cylinder, Cone, Plane)
 
 
 def csg_program(obj):
@@ -288,8 +288,9 @@ def convert(args: RenderArgs) -> abi.PackedScene:
         if key not in prog_index:
             from .gml.surface_compiler import compile_surface
             stack = args.state.stack if args.state is not None else ()
+            ext = bool(getattr(args.state, "extensions", False))
             prog_index[key] = len(programs)
-            programs.append((sf, compile_surface(sf, stack)))
+            programs.append((sf, compile_surface(sf, stack, ext)))
         return -(prog_index[key] + 1)
 
     def fill(co, o):

@@ -61,7 +61,7 @@ extern "C" {
 /* Contest extension (GML `intersect` / `difference`; the reference renderer
  * rejects Difference, raytracer.go:825-826): one composite solid. Its leaves
  * are rt_scene.csg_leaves[csg_first .. csg_first + csg_count) (spheres, cubes,
- * cylinders, planes as half-spaces n.p + D <= 0) combined by a postfix program
+ * cylinders, cones, planes as half-spaces n.p + D <= 0) combined by a postfix program
  * rt_scene.csg_code[csg_code .. csg_code + csg_code_len): v >= 0 pushes leaf v
  * (relative to csg_first), RT_CSG_UNION / _INTERSECT / _DIFFERENCE pop two.
  * The hit is the first interval end point t > 0 at which the composite's
@@ -180,6 +180,13 @@ typedef struct rt_light {
 #define RT_VM_NOT 29
 #define RT_VM_ERR 30   /* the evaluation fails (counted in surface_errors) if r[a] != 0 */
 #define RT_VM_RET 31
+/* Contest extensions (GML `asin`, `acos`, `real`; not in the reference's
+ * interpreter, oracle-pinned through the host interpreter). Angles come out
+ * in degrees: one product with 57.29577951308232 (180 / Pi rounded once),
+ * mirroring how SIN / COS apply Pi / 180. NaN for |x| > 1, as Go's math.Asin. */
+#define RT_VM_EXT_ASIN 32 /* r[d] = 57.29577951308232 * Go math.Asin(r[a]) */
+#define RT_VM_EXT_ACOS 33 /* r[d] = 57.29577951308232 * Go math.Acos(r[a]) */
+#define RT_VM_EXT_REAL 34 /* r[d] = float64(int64 r[a]) (round to nearest even) */
 #define RT_VM_INSN(op, d, a, b) ((uint32_t)(op) | ((uint32_t)(d) << 8) | ((uint32_t)(a) << 16) | ((uint32_t)(b) << 24))
 
 typedef struct rt_object {
