@@ -5,6 +5,8 @@ sizes and offsets against the compiled library's expectations.
 """
 import ctypes as C
 
+import numpy as np
+
 RT_ABI_VERSION = 6  # include/rt_abi.h
 RT_MAX_DEVICES = 16
 RT_EXP_AMD64_FMA, RT_EXP_AMD64, RT_EXP_PORTABLE = 0, 1, 2  # rt_scene.exp_mode
@@ -179,6 +181,39 @@ class rt_render_opts(C.Structure):
         ("bands", C.c_int32),
         ("reserved", C.c_int32 * 5),
     ]
+
+
+class rt_ray(C.Structure):
+    """One query ray (rt_query_*_async): 64 bytes, arrays 16-byte aligned."""
+    _fields_ = [
+        ("origin", C.c_double * 3),
+        ("dir", C.c_double * 3),  # used as given: t is in units of |dir|
+        ("tmax", C.c_double),     # a result counts when T < tmax (+inf: no limit)
+        ("exclude", C.c_int32),   # top-level object index left out, -1: none
+        ("reserved", C.c_int32),
+    ]
+
+
+class rt_hit(C.Structure):
+    """One closest-hit record: 96 bytes. A miss is object = -1 and zero elsewhere."""
+    _fields_ = [
+        ("t", C.c_double),
+        ("point_obj", C.c_double * 3),
+        ("point_world", C.c_double * 3),
+        ("normal_world", C.c_double * 3),
+        ("object", C.c_int32),
+        ("face", C.c_int32),      # composites: (leaf << 4) | (flip << 3) | leaf_face
+        ("kind", C.c_int32),      # of the surface (the leaf's for a composite)
+        ("material", C.c_int32),  # >= 0 material index, < 0 closure program -(p+1)
+    ]
+
+
+# numpy structured dtypes of the same layout as rt_ray / rt_hit
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("tmax", "<f8"), ("exclude", "<i4"),
+                      ("reserved", "<i4")])
+HIT_DTYPE = np.dtype([("t", "<f8"), ("point_obj", "<f8", (3,)), ("point_world", "<f8", (3,)),
+                      ("normal_world", "<f8", (3,)), ("object", "<i4"), ("face", "<i4"), ("kind", "<i4"),
+                      ("material", "<i4")])
 
 
 class PackedScene:

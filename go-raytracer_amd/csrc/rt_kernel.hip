@@ -2814,4 +2814,5 @@ int rt_debug_run_surface(rt_context* c, int program, int n, const long long* fac
 }  // extern "C"
 
 #include "rt_ssim.hip"
+#include "rt_query.hip"
 #include "rt_render_api.hip"

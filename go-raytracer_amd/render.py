@@ -91,6 +91,10 @@ def load_library(path=None):
     l.rt_debug_spec_compile.restype = i
     l.rt_debug_getenv.argtypes = [C.c_char_p]
     l.rt_debug_getenv.restype = C.c_char_p
+    l.rt_query_closest_async.argtypes = [vp, i, vp, vp, vp]
+    l.rt_query_closest_async.restype = i
+    l.rt_query_occluded_async.argtypes = [vp, i, vp, vp, vp]
+    l.rt_query_occluded_async.restype = i
     if l.rt_abi_version() != abi.RT_ABI_VERSION:
         raise RenderError("librtamd ABI version mismatch")
     _lib = l
@@ -288,6 +292,71 @@ class RenderContext:
         self.render_rows_async(y0, y1, out)
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy()
+
+    # ---- batched ray queries (include/rt_abi.h rt_query_*_async) ----
+    def _query_args(self, rays, out, out_bytes, what):
+        torch = self.torch
+        for t, name in ((rays, "rays"), (out, "output")):
+            assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous(), \
+                "%s: %s must be a contiguous uint8 CUDA tensor" % (what, name)
+            assert t.device.index == self.device, "%s: %s is on another device" % (what, name)
+        rec = abi.RAY_DTYPE.itemsize
+        assert rays.numel() % rec == 0, "%s: rays must hold whole %d-byte records" % (what, rec)
+        n = rays.numel() // rec
+        assert out.numel() == n * out_bytes, "%s: output tensor size does not match %d rays" % (what, n)
+        return n
+
+    def query_closest_async(self, rays, hits, stream=None):
+        """Enqueue closest-hit queries: `rays` a uint8 CUDA tensor of n * 64
+        bytes (abi.RAY_DTYPE records), `hits` one of n * 96 bytes
+        (abi.HIT_DTYPE), against the current scene, ordered on `stream`."""
+        n = self._query_args(rays, hits, abi.HIT_DTYPE.itemsize, "query_closest_async")
+        s = self.torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_query_closest_async(self.handle, n, C.c_void_p(rays.data_ptr()),
+                                               C.c_void_p(hits.data_ptr()), C.c_void_p(s.cuda_stream)),
+               "rt_query_closest_async")
+
+    def query_occluded_async(self, rays, out, stream=None):
+        """Enqueue occlusion queries: out[i] = 1 when ray i meets any object
+        other than its `exclude` at T < tmax. `out`: a uint8 CUDA tensor of n bytes."""
+        n = self._query_args(rays, out, 1, "query_occluded_async")
+        s = self.torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_query_occluded_async(self.handle, n, C.c_void_p(rays.data_ptr()),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)),
+               "rt_query_occluded_async")
+
+    def _upload_rays(self, origins, dirs, tmax, exclude):
+        o = np.asarray(origins, dtype=np.float64)
+        d = np.asarray(dirs, dtype=np.float64)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("origins and dirs must both be [n, 3] arrays")
+        n = o.shape[0]
+        rec = np.zeros(n, dtype=abi.RAY_DTYPE)
+        rec["origin"] = o
+        rec["dir"] = d
+        rec["tmax"] = np.inf if tmax is None else np.broadcast_to(np.asarray(tmax, dtype=np.float64), (n,))
+        rec["exclude"] = -1 if exclude is None else np.broadcast_to(np.asarray(exclude, dtype=np.int32), (n,))
+        dev = "cuda:%d" % self.device
+        return n, self.torch.from_numpy(rec.view(np.uint8).reshape(-1)).to(dev)
+
+    def closest_hits(self, origins, dirs, tmax=None, exclude=None):
+        """Synchronous closest-hit queries for numpy [n, 3] float64 origins and
+        directions (tmax, exclude: None, a scalar or [n]) -> abi.HIT_DTYPE array [n]."""
+        torch = self.torch
+        n, rays = self._upload_rays(origins, dirs, tmax, exclude)
+        hits = torch.empty(n * abi.HIT_DTYPE.itemsize, dtype=torch.uint8, device=rays.device)
+        self.query_closest_async(rays, hits)
+        torch.cuda.synchronize(self.device)
+        return hits.cpu().numpy().view(abi.HIT_DTYPE)
+
+    def occluded(self, origins, dirs, tmax=None, exclude=None):
+        """Synchronous occlusion queries (arguments as closest_hits) -> bool array [n]."""
+        torch = self.torch
+        n, rays = self._upload_rays(origins, dirs, tmax, exclude)
+        out = torch.empty(n, dtype=torch.uint8, device=rays.device)
+        self.query_occluded_async(rays, out)
+        torch.cuda.synchronize(self.device)
+        return out.cpu().numpy().astype(bool)
 
 
 def kernel_source_id():

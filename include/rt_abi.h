@@ -474,6 +474,49 @@ const char *rt_debug_getenv(const char *name);
 int rt_debug_run_surface(rt_context *ctx, int program, int n, const long long *face,
                          const double *u, const double *v, double *out10, int *err);
 
+/* ---- Batched ray queries against the scene last given to rt_set_scene ----
+ * A separate kernel (csrc/rt_query.hip), one ray per lane, running the same
+ * exact Intersect code as the renderer. Both records live in device memory,
+ * in arrays aligned to 16 bytes. */
+typedef struct rt_ray {        /* 64 bytes */
+    double  origin[3];
+    double  dir[3];            /* used as given, never normalised: t is in units of |dir| */
+    double  tmax;              /* only an Intersect result with T < tmax counts; +inf: no limit */
+    int32_t exclude;           /* top-level object index left out (raytracer.go:416), -1: none */
+    int32_t reserved;          /* 0 */
+} rt_ray;
+
+typedef struct rt_hit {        /* 96 bytes */
+    double  t;
+    double  point_obj[3];      /* Hit.PointObj: object space of the surface (of the leaf, for a composite) */
+    double  point_world[3];    /* HitEx.PointWorld */
+    double  normal_world[3];   /* HitEx.NormalWorld, as the reference leaves it (a sphere's is not unit length) */
+    int32_t object;            /* top-level index, -1: miss */
+    int32_t face;              /* the oracle's code; composites: (leaf << 4) | (flip << 3) | leaf_face */
+    int32_t kind;              /* RT_SPHERE.. of the surface (the leaf's kind for a composite) */
+    int32_t material;          /* the face's objmat entry: >= 0 material index, < 0 closure program -(p+1) */
+} rt_hit;
+
+/* Closest mode: closestHit (raytracer.go:469-483) over the top-level objects
+ * in index order for each of the n rays. Each object's own Intersect decides
+ * whether there is a hit (its own t > 0 rules); `exclude` is skipped; a result
+ * counts when T < tmax; the smallest T wins and exact ties go to the lowest
+ * index. A miss writes object = -1 and zero in every other field, so records
+ * compare as bytes. The answer does not depend on rt_set_accel.
+ * RT_E_INVALID (with an rt_last_error text): NULL context, no scene set,
+ * n < 0, or n > 0 with a NULL or not 16-byte aligned d_rays / d_hits. n == 0
+ * returns RT_OK and launches nothing. The launch is ordered on `stream`; it
+ * touches neither the frame counters (rt_read_stats) nor the tile order, the
+ * specialisation state or pending compiles. As for renders, the scene must
+ * not be replaced while a query is in flight. */
+int rt_query_closest_async(rt_context *ctx, int n, const rt_ray *d_rays, rt_hit *d_hits, void *stream);
+
+/* Occluded mode: d_occluded[i] = 1 when any object other than `exclude` has an
+ * Intersect result with T < tmax for ray i, else 0 -- inShadow's loop
+ * (raytracer.go:411-429) with the caller supplying the bound. Errors, ordering
+ * and side effects as rt_query_closest_async (d_occluded needs no alignment). */
+int rt_query_occluded_async(rt_context *ctx, int n, const rt_ray *d_rays, uint8_t *d_occluded, void *stream);
+
 /* SSIM of two RGBA8 frames in device memory (width x height, stride 4W), the
  * reference's parity metric prim.SSIM (internal/prim/ssim.go:27-182; used by
  * raytracer_test.go:42 with threshold 0.99). Synchronous on `stream`.
