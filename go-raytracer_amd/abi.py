@@ -208,12 +208,24 @@ class rt_hit(C.Structure):
     ]
 
 
-# numpy structured dtypes of the same layout as rt_ray / rt_hit
+class rt_radiance(C.Structure):
+    """One radiance record (rt_query_radiance_async): 32 bytes."""
+    _fields_ = [
+        ("color", C.c_double * 3),  # what traceRay returns for the ray
+        ("object", C.c_int32),      # top-level object the ray itself hit, -1: background
+        ("rays", C.c_int32),        # rays traced for this query (1 + secondary rays)
+    ]
+
+
+RT_RADIANCE_MAX_DEPTH = 32
+
+# numpy structured dtypes of the same layout as rt_ray / rt_hit / rt_radiance
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("tmax", "<f8"), ("exclude", "<i4"),
                       ("reserved", "<i4")])
 HIT_DTYPE = np.dtype([("t", "<f8"), ("point_obj", "<f8", (3,)), ("point_world", "<f8", (3,)),
                       ("normal_world", "<f8", (3,)), ("object", "<i4"), ("face", "<i4"), ("kind", "<i4"),
                       ("material", "<i4")])
+RADIANCE_DTYPE = np.dtype([("color", "<f8", (3,)), ("object", "<i4"), ("rays", "<i4")])
 
 
 class PackedScene:

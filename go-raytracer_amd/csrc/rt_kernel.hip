@@ -606,6 +606,10 @@ struct rt_context {
   bool spec_failed = false;    // its compile (or one of a launch's schedule variants) failed
   std::string spec_err;        // ... with this message
   bool last_spec = false;      // the last render launch ran a specialised kernel
+  // radiance queries (rt_trace.hip): the lanes' frame stacks, grown on demand, and the ticket counter
+  double* trace_ws = nullptr;
+  size_t trace_ws_bytes = 0;
+  unsigned int* trace_ticket = nullptr;
 };
 
 namespace {
@@ -1586,6 +1590,8 @@ void rt_destroy(rt_context* c) {
   (void)hipFree(c->gboard);
   (void)hipFree(c->gring);
   (void)hipFree(c->gctl);
+  (void)hipFree(c->trace_ws);
+  (void)hipFree(c->trace_ticket);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   delete c;
@@ -2815,4 +2821,5 @@ int rt_debug_run_surface(rt_context* c, int program, int n, const long long* fac
 
 #include "rt_ssim.hip"
 #include "rt_query.hip"
+#include "rt_trace.hip"
 #include "rt_render_api.hip"

@@ -95,6 +95,12 @@ def load_library(path=None):
     l.rt_query_closest_async.restype = i
     l.rt_query_occluded_async.argtypes = [vp, i, vp, vp, vp]
     l.rt_query_occluded_async.restype = i
+    l.rt_query_radiance_async.argtypes = [vp, i, vp, i, vp, vp]
+    l.rt_query_radiance_async.restype = i
+    l.rt_query_radiance_lanes.argtypes = [vp, i]
+    l.rt_query_radiance_lanes.restype = i
+    l.rt_query_camera_rays_async.argtypes = [vp, i, i, vp, vp]
+    l.rt_query_camera_rays_async.restype = i
     if l.rt_abi_version() != abi.RT_ABI_VERSION:
         raise RenderError("librtamd ABI version mismatch")
     _lib = l
@@ -357,6 +363,93 @@ class RenderContext:
         self.query_occluded_async(rays, out)
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy().astype(bool)
+
+    # ---- radiance queries (include/rt_abi.h rt_query_radiance_async) ----
+    def query_radiance_async(self, rays, out, depth=0, stream=None):
+        """Enqueue radiance queries: out[i] = traceRay(rays[i], depth) against
+        the current scene (depth 0: the scene's). `rays` as for
+        query_closest_async, `out` a uint8 CUDA tensor of n * 32 bytes
+        (abi.RADIANCE_DTYPE). Radiance queries on one context share a
+        workspace: keep them ordered with respect to each other."""
+        n = self._query_args(rays, out, abi.RADIANCE_DTYPE.itemsize, "query_radiance_async")
+        s = self.torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_query_radiance_async(self.handle, n, C.c_void_p(rays.data_ptr()), int(depth),
+                                                C.c_void_p(out.data_ptr()), C.c_void_p(s.cuda_stream)),
+               "rt_query_radiance_async")
+
+    def radiance_lanes(self, depth=0):
+        """Lanes of the persistent grid a radiance query at `depth` runs on at most."""
+        n = self.lib.rt_query_radiance_lanes(self.handle, int(depth))
+        if n < 0:
+            _check(n, "rt_query_radiance_lanes")
+        return n
+
+    def radiance(self, origins, dirs, depth=None, tmax=None, exclude=None):
+        """Synchronous radiance queries for numpy [n, 3] float64 origins and
+        directions (depth None: the scene's; tmax, exclude as closest_hits)
+        -> abi.RADIANCE_DTYPE array [n]."""
+        torch = self.torch
+        n, rays = self._upload_rays(origins, dirs, tmax, exclude)
+        out = torch.empty(n * abi.RADIANCE_DTYPE.itemsize, dtype=torch.uint8, device=rays.device)
+        self.query_radiance_async(rays, out, 0 if depth is None else depth)
+        torch.cuda.synchronize(self.device)
+        return out.cpu().numpy().view(abi.RADIANCE_DTYPE)
+
+    def camera_rays_async(self, y0, y1, out, stream=None):
+        """Enqueue the reference camera's rays of rows [y0, y1): `out` a uint8
+        CUDA tensor of (y1 - y0) * W * 4 records of 64 bytes (abi.RAY_DTYPE),
+        in [row][x][sample] order."""
+        torch = self.torch
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous(), \
+            "camera_rays_async: out must be a contiguous uint8 CUDA tensor"
+        assert out.device.index == self.device, "camera_rays_async: out is on another device"
+        rows = max(0, int(y1) - int(y0))
+        assert out.numel() == rows * self.packed.width * 4 * abi.RAY_DTYPE.itemsize, \
+            "camera_rays_async: output tensor size does not match %d rows" % rows
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_query_camera_rays_async(self.handle, int(y0), int(y1), C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(s.cuda_stream)), "rt_query_camera_rays_async")
+
+    def camera_rays(self, y0=0, y1=None):
+        """Synchronous camera rays of rows [y0, y1) -> numpy abi.RAY_DTYPE array [rows, W, 4]."""
+        torch = self.torch
+        if y1 is None:
+            y1 = self.packed.height
+        w = self.packed.width
+        rows = max(0, y1 - y0)
+        out = torch.empty(rows * w * 4 * abi.RAY_DTYPE.itemsize, dtype=torch.uint8, device="cuda:%d" % self.device)
+        self.camera_rays_async(y0, y1, out)
+        torch.cuda.synchronize(self.device)
+        return out.cpu().numpy().view(abi.RAY_DTYPE).reshape(rows, w, 4)
+
+    def image_from_radiance(self, out, samples):
+        """Average `samples` consecutive radiance records per pixel and quantise
+        as Render() does (raytracer.go:651-656, vec.go:104-107): `out` a uint8
+        CUDA tensor of rows * W * samples records -> uint8 [rows, W, 4] CUDA
+        tensor. The samples are added in order, ((s0 + s1) + s2) + ..., in
+        float64, then scaled by 1.0 / samples."""
+        torch = self.torch
+        rec = abi.RADIANCE_DTYPE.itemsize
+        w = self.packed.width
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous(), \
+            "image_from_radiance: out must be a contiguous uint8 CUDA tensor"
+        assert samples >= 1 and out.numel() % (rec * w * samples) == 0, \
+            "image_from_radiance: out must hold rows * W * samples records"
+        rows = out.numel() // (rec * w * samples)
+        col = out.view(torch.float64).view(rows, w, samples, rec // 8)[..., :3]
+        total = col[:, :, 0, :].clone()
+        for k in range(1, samples):
+            total = total + col[:, :, k, :]
+        c = total * (1.0 / samples)
+        # uint32(c * 65535) >> 8 as Go converts on amd64: through int64, truncated
+        # to 32 bits; NaN and values outside (-2^63, 2^63) give 0
+        v = c * 65535.0
+        ok = (v > -9223372036854775808.0) & (v < 9223372036854775808.0)
+        q = (torch.where(ok, v, torch.zeros_like(v)).to(torch.int64) & 0xffffffff) >> 8
+        img = torch.empty((rows, w, 4), dtype=torch.uint8, device=out.device)
+        img[..., :3] = (q & 0xff).to(torch.uint8)
+        img[..., 3] = 255
+        return img
 
 
 def kernel_source_id():

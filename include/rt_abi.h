@@ -517,6 +517,61 @@ int rt_query_closest_async(rt_context *ctx, int n, const rt_ray *d_rays, rt_hit 
  * and side effects as rt_query_closest_async (d_occluded needs no alignment). */
 int rt_query_occluded_async(rt_context *ctx, int n, const rt_ray *d_rays, uint8_t *d_occluded, void *stream);
 
+/* ---- Radiance queries: traceRay for arbitrary rays, and the camera's rays ----
+ * A separate kernel (csrc/rt_trace.hip) with the renderer's exact tests and
+ * shading, so a query returns the colour Render() sums for that ray, bit for
+ * bit. */
+typedef struct rt_radiance {   /* 32 bytes, arrays 16-byte aligned */
+    double  color[3];          /* what traceRay returns for the ray (clamped per level as the reference does) */
+    int32_t object;            /* top-level object the ray itself hit, -1: background */
+    int32_t rays;              /* rays traced for this query: 1 + all secondary rays actually traced */
+} rt_radiance;
+
+#define RT_RADIANCE_MAX_DEPTH 32
+
+/* d_out[i] = traceRay(d_rays[i], depth) (raytracer.go:487-562) against the
+ * scene last set: lighting, shadows, the fuzz offset, reflection, refraction,
+ * Fresnel, closure surfaces and CSG. depth == 0 means the scene's depth (3
+ * when the scene gave depth <= 0). The direction is used as given, never
+ * normalised (V = -dir, inShadow's t * |dir| < dist and fresnel's cosine
+ * similarity then see the non-unit direction, as in the reference). tmax and
+ * exclude apply to the ray's own closestHit only, with their meaning in
+ * rt_query_closest_async; secondary and shadow rays follow the reference.
+ * `rays` counts a ray when traceRay is entered with depth > 0, so depth 1
+ * always answers rays == 1. The answer does not depend on rt_set_accel.
+ * RT_E_INVALID (with an rt_last_error text): NULL context, no scene set,
+ * n < 0, depth < 0 or > RT_RADIANCE_MAX_DEPTH (also a scene depth above it
+ * with depth == 0), or n > 0 with a NULL or not 16-byte aligned d_rays /
+ * d_out. n == 0 returns RT_OK and launches nothing. The launch is ordered on
+ * `stream` and touches neither the frame counters (rt_read_stats) nor the tile
+ * order, the specialisation state or pending compiles.
+ * Unlike the other queries the call uses a per-context workspace: the frame
+ * stacks of a persistent grid of rt_query_radiance_lanes() lanes (depth - 1
+ * frames of 120 bytes per lane, at most 128 MiB per context: deeper calls run
+ * on fewer lanes), allocated at the first call, grown when a call needs more
+ * (which waits for the device) and freed by rt_destroy. Radiance queries on
+ * one context must therefore be ordered with respect to each other -- one
+ * stream, or events between streams -- as renders on a context already are. */
+int rt_query_radiance_async(rt_context *ctx, int n, const rt_ray *d_rays, int depth,
+                            rt_radiance *d_out, void *stream);
+
+/* Lanes of the persistent grid a radiance query at `depth` (0: the scene's)
+ * runs on at most -- 512 per compute unit, fewer where the workspace bound
+ * says so; a batch of n rays uses min(that, n rounded up to 256). A batch
+ * larger than this makes lanes take several rays. Negative: RT_E_INVALID. */
+int rt_query_radiance_lanes(rt_context *ctx, int depth);
+
+/* The reference camera's rays (raytracer.go:605-652) for rows [y0, y1) of the
+ * scene's frame: 4 * width * (y1 - y0) records in [row][x][sample] order with
+ * tmax = +inf, exclude = -1, reserved = 0 -- the exact jitter draws of
+ * Render() (PCG seeded per column and 20-row strip, 8 draws per row, the
+ * draws of a strip's rows before y0 consumed), so averaging their radiance at
+ * the scene's depth and quantising reproduces Render()'s pixels.
+ * RT_E_INVALID: NULL context, no scene set, rows outside 0 <= y0 < y1 <=
+ * height, NULL or not 16-byte aligned d_rays. Ordered on `stream`; no side
+ * effects on the context. */
+int rt_query_camera_rays_async(rt_context *ctx, int y0, int y1, rt_ray *d_rays, void *stream);
+
 /* SSIM of two RGBA8 frames in device memory (width x height, stride 4W), the
  * reference's parity metric prim.SSIM (internal/prim/ssim.go:27-182; used by
  * raytracer_test.go:42 with threshold 0.99). Synchronous on `stream`.
