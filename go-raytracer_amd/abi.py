@@ -219,6 +219,35 @@ class rt_radiance(C.Structure):
 
 RT_RADIANCE_MAX_DEPTH = 32
 
+# camera renders (rt_camera_rays_async, rt_render_camera_async)
+RT_CAMERA_PINHOLE, RT_CAMERA_ORTHO, RT_CAMERA_EQUIRECT, RT_CAMERA_THINLENS = 0, 1, 2, 3
+RT_CAMERA_POSED = 1  # rt_camera.flags
+RT_CAMERA_MAX_SAMPLES = 1024
+CAMERA_MODELS = {"pinhole": RT_CAMERA_PINHOLE, "ortho": RT_CAMERA_ORTHO, "equirect": RT_CAMERA_EQUIRECT,
+                 "thinlens": RT_CAMERA_THINLENS}
+
+
+class rt_camera(C.Structure):
+    """A camera render's camera. All zero = the scene's own camera at 4
+    samples: Render()."""
+    _fields_ = [
+        ("model", C.c_int32),         # RT_CAMERA_*
+        ("flags", C.c_int32),         # RT_CAMERA_POSED: eye / look_at / up are given
+        ("samples", C.c_int32),       # per pixel, 1..RT_CAMERA_MAX_SAMPLES; 0: 4
+        ("width", C.c_int32),         # both 0: the scene's; else both >= 2
+        ("height", C.c_int32),
+        ("depth", C.c_int32),         # 0: the scene's
+        ("chunk_pixels", C.c_int32),  # 0: automatic; > 0: at most this many pixels per launch
+        ("reserved", C.c_int32),
+        ("fov", C.c_double),          # degrees; <= 0: the scene's
+        ("extent", C.c_double),       # ortho: world width of the view
+        ("aperture", C.c_double),     # thin lens: lens diameter
+        ("focus", C.c_double),        # thin lens: focal-plane distance
+        ("eye", C.c_double * 3),
+        ("look_at", C.c_double * 3),
+        ("up", C.c_double * 3),
+    ]
+
 # numpy structured dtypes of the same layout as rt_ray / rt_hit / rt_radiance
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("tmax", "<f8"), ("exclude", "<i4"),
                       ("reserved", "<i4")])

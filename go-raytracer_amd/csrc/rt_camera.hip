@@ -1,0 +1,365 @@
+// rt_camera.hip -- camera renders (include/rt_abi.h rt_camera,
+// rt_camera_rays_async, rt_render_camera_async, rt_render_camera_chunks).
+//
+// The radiance kernel of rt_trace.hip with a ray source of its own, plus a
+// resolve step. rt_trace_kernel<.., GEN = true> hands out tickets exactly as a
+// radiance query does, but ticket t is sample t % S of pixel first + t / S of
+// the camera's frame, and the lane that takes it forms the ray itself
+// (cam_ticket_ray -> cam_ray) instead of loading Q.rays[t]. Everything after
+// the refill is the query's code, and the record still goes to Q.out[t]: here
+// the context's sample buffer. cam_resolve_kernel, one thread per pixel, then
+// adds the pixel's S records in sample order, scales and quantises.
+//
+// Sample-granular tickets and a separate resolve, not a per-lane accumulator
+// over a pixel's samples: nothing new stays live across the kernel's loop
+// (pixel, sample, draws and the camera-space ray die inside the refill; the
+// camera is a kernel argument, read through scalar loads where it is needed),
+// and the kernel's CSG and VM instantiations have no registers to spare.
+//
+// Bounded memory: a band is cut into chunks of consecutive pixels whose
+// samples fit the buffer (CAM_BUF_RECORDS records, 64 MiB). Per chunk, on the
+// caller's stream: zero the ticket, one GEN launch, one resolve launch. The
+// stream orders a chunk's resolve after its trace and the next chunk's trace
+// after that resolve, so one buffer and one ticket serve every chunk and the
+// host never waits. Within a launch the ticket counter is still the only state
+// waves share: a wave's loop ends when its lanes hold no ray and every ticket
+// has been handed out, each ray tree is bounded by the depth, and no wave
+// waits for another -- nothing can hang, as for the radiance queries.
+//
+// PCG position: sample s of row y starts ((y mod 20) * S + s) * D draws into
+// its column's strip stream (D draws per sample), at most 81 916 < 2^17. The
+// lane jumps there by binary decomposition: the LCG's 2^k-step maps (A, C),
+// k = 0..16, are compile-time constants, and the lane applies the maps of the
+// set bits of its offset (pcg_jump, as the render kernel does with its
+// host-built table).
+// Included by rt_kernel.hip after rt_trace.hip.
+
+namespace {
+
+constexpr int CAM_BUF_RECORDS = 2097152;  // rt_radiance records of the sample buffer, at most (64 MiB)
+constexpr int CAM_JUMP_BITS = 17;         // offsets below 2^17: 19 * 1024 * 4 + 1023 * 4 = 81 916
+
+struct CamJumpPow {
+  uint64_t v[CAM_JUMP_BITS][4];  // [k]: ahi alo chi clo of 2^k LCG steps
+};
+
+constexpr CamJumpPow cam_jump_pow() {
+  typedef unsigned __int128 u128;
+  const u128 mul = ((u128)2549297995355413924ULL << 64) | 4865540595714422341ULL;  // pcg.go
+  const u128 inc = ((u128)6364136223846793005ULL << 64) | 1442695040888963407ULL;
+  CamJumpPow t = {};
+  u128 A = mul, Cc = inc;
+  for (int k = 0; k < CAM_JUMP_BITS; k++) {
+    t.v[k][0] = (uint64_t)(A >> 64);
+    t.v[k][1] = (uint64_t)A;
+    t.v[k][2] = (uint64_t)(Cc >> 64);
+    t.v[k][3] = (uint64_t)Cc;
+    Cc = Cc * A + Cc;  // twice the steps: x -> A (A x + C) + C
+    A = A * A;
+  }
+  return t;
+}
+
+__constant__ const CamJumpPow k_cam_jump = cam_jump_pow();
+
+// The camera of a launch, derived on the host (cam_setup): wave-uniform.
+struct CamArgs {
+  int model, posed;
+  int S, D;       // samples per pixel, draws per sample
+  int W, H;       // the camera's frame
+  int first;      // frame pixel (y * W + x) of ticket 0 / of the rays kernel's first row
+  int nbits;      // bit length of the largest draw offset: 19 * S * D + (S - 1) * D
+  double W1, H1;  // float(W - 1), float(H - 1)
+  double vw, vh;
+  double half_ap, focus;               // thin lens: aperture / 2, focal-plane distance
+  double eye[3], r[3], w[3], f[3];     // posed: the eye and the basis (right, up, forward)
+};
+
+template <>
+struct TraceArgsT<true> : TraceArgs {
+  CamArgs cam;
+};
+
+// Sample s of frame pixel `pixel`: the ray of include/rt_abi.h "Camera
+// renders", operation for operation. The one ray-forming function: the GEN
+// refill of rt_trace_kernel and cam_rays_kernel both call it.
+__device__ __forceinline__ void cam_ray(const CamArgs& A, int pixel, int s, d3& ro, d3& rd) {
+  const int y = pixel / A.W, x = pixel - y * A.W;
+  const int ry = y % 20;
+  Pcg rng{0xDEADULL ^ (uint64_t)x, 0xBEEFULL ^ (uint64_t)(y - ry)};  // raytracer.go:632-634
+  const unsigned int off = ((unsigned int)ry * (unsigned int)A.S + (unsigned int)s) * (unsigned int)A.D;
+  for (int k = 0; k < A.nbits; k++) {  // (wave-uniform k: the table through scalar loads)
+    const uint64_t* j = k_cam_jump.v[k];
+    if ((off >> k) & 1u) rng = pcg_jump(rng, j[0], j[1], j[2], j[3]);
+  }
+  const double dx = pcg_float64(rng) - 0.5;
+  const double dy = pcg_float64(rng) - 0.5;
+  const double su = ((double)x + dx) / A.W1;
+  const double sv = ((double)y + dy) / A.H1;
+  const d3 e = mk(0.0, 0.0, -1.0);  // raytracer.go:605-609
+  d3 o, d;
+  if (A.model == RT_CAMERA_EQUIRECT) {
+    const double th = (su - 0.5) * 360.0, ph = (0.5 - sv) * 180.0;
+    const double st = rt::go_sin(0.017453292519943295 * th), ct = rt::go_cos(0.017453292519943295 * th);
+    const double sp = rt::go_sin(0.017453292519943295 * ph), cp = rt::go_cos(0.017453292519943295 * ph);
+    o = e;
+    d = mk(st * cp, sp, ct * cp);
+  } else {
+    const double u = su * A.vw - A.vw / 2.0;
+    const double v = sv * A.vh - A.vh / 2.0;
+    o = mk(u, -v, 0.0);
+    if (A.model == RT_CAMERA_ORTHO) {
+      d = mk(0.0, 0.0, 1.0);
+    } else {
+      d = norm(sub(o, e));
+      if (A.model == RT_CAMERA_THINLENS) {
+        const double d2 = pcg_float64(rng), d3_ = pcg_float64(rng);
+        const d3 P = add(e, scale(d, A.focus / d.z));
+        const double rho = A.half_ap * __builtin_sqrt(d2), al = 360.0 * d3_;
+        const double ca = rt::go_cos(0.017453292519943295 * al), sa = rt::go_sin(0.017453292519943295 * al);
+        const d3 L = add(e, mk(rho * ca, rho * sa, 0.0));
+        o = L;
+        d = norm(sub(P, L));
+      }
+    }
+  }
+  if (A.posed) {
+    const double pz = o.z + 1.0;
+    ro = mk(A.eye[0] + o.x * A.r[0] + o.y * A.w[0] + pz * A.f[0], A.eye[1] + o.x * A.r[1] + o.y * A.w[1] + pz * A.f[1],
+            A.eye[2] + o.x * A.r[2] + o.y * A.w[2] + pz * A.f[2]);
+    rd = mk(d.x * A.r[0] + d.y * A.w[0] + d.z * A.f[0], d.x * A.r[1] + d.y * A.w[1] + d.z * A.f[1],
+            d.x * A.r[2] + d.y * A.w[2] + d.z * A.f[2]);
+  } else {
+    ro = o;
+    rd = d;
+  }
+}
+
+// Ticket t of a GEN launch (t < n <= CAM_BUF_RECORDS)
+__device__ __forceinline__ void cam_ticket_ray(const CamArgs& A, unsigned int t, d3& ro, d3& rd) {
+  const unsigned int p = t / (unsigned int)A.S;
+  cam_ray(A, A.first + (int)p, (int)(t - p * (unsigned int)A.S), ro, rd);
+}
+
+// rt_camera_rays_async: one thread per (pixel, sample) of the band
+__global__ __launch_bounds__(WG) void cam_rays_kernel(CamArgs A, long long n, rt_ray* out) {
+  const long long tid = (long long)blockIdx.x * WG + threadIdx.x;
+  if (tid >= n) return;
+  const long long p = tid / A.S;
+  d3 o, d;
+  cam_ray(A, A.first + (int)p, (int)(tid - p * A.S), o, d);
+  Q16* rp = reinterpret_cast<Q16*>(out + tid);
+  const Q16 r0 = {o.x, o.y}, r1 = {o.z, d.x}, r2 = {d.y, d.z};
+  rp[0] = r0;
+  rp[1] = r1;
+  rp[2] = r2;
+  const R16 r3 = {__builtin_inf(), -1, 0};
+  *reinterpret_cast<R16*>(rp + 3) = r3;
+}
+
+// One thread per pixel of a chunk: the pixel's S records (two 16-byte loads
+// each) added in sample order, scaled by 1 / S, quantised as Render() does.
+// `px0`: the chunk's first pixel relative to the band (the outputs' origin).
+__global__ __launch_bounds__(WG) void cam_resolve_kernel(const rt_radiance* __restrict__ rec, int npix, int S,
+                                                          double inv, long long px0, uint32_t* rgba, double* mean) {
+  const int p = (int)(blockIdx.x * WG + threadIdx.x);
+  if (p >= npix) return;
+  const Q16* rp = reinterpret_cast<const Q16*>(rec + (size_t)p * S);
+  Q16 a = rp[0], b = rp[1];
+  d3 sum = mk(a.a, a.b, b.a);
+  for (int s = 1; s < S; s++) {
+    a = rp[2 * s];
+    b = rp[2 * s + 1];
+    sum = add(sum, mk(a.a, a.b, b.a));
+  }
+  const d3 c = scale(sum, inv);
+  const long long q = px0 + p;
+  if (mean) {
+    mean[q * 3 + 0] = c.x;
+    mean[q * 3 + 1] = c.y;
+    mean[q * 3 + 2] = c.z;
+  }
+  if (rgba) {
+    const uint32_t r8 = go_f64_to_u32(c.x * 65535.0) >> 8;
+    const uint32_t g8 = go_f64_to_u32(c.y * 65535.0) >> 8;
+    const uint32_t b8 = go_f64_to_u32(c.z * 65535.0) >> 8;
+    rgba[q] = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
+  }
+}
+
+// [BVH | CSG << 1 | VM << 2], as k_trace_kernels
+const void* const k_camera_kernels[8] = {
+    (const void*)rt_trace_kernel<false, false, false, true>, (const void*)rt_trace_kernel<true, false, false, true>,
+    (const void*)rt_trace_kernel<false, true, false, true>,  (const void*)rt_trace_kernel<true, true, false, true>,
+    (const void*)rt_trace_kernel<false, false, true, true>,  (const void*)rt_trace_kernel<true, false, true, true>,
+    (const void*)rt_trace_kernel<false, true, true, true>,   (const void*)rt_trace_kernel<true, true, true, true>};
+
+struct CamPlan {
+  CamArgs A;
+  int depth;         // of the trace
+  long long pixels;  // of the band
+  int chunk;         // pixels per chunk
+  int chunks;
+};
+
+bool cam_finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+// Validate `cam` (NULL: all zeros) and the rows against the context's scene
+// and derive the launch's camera, in the order include/rt_abi.h states.
+int cam_setup(rt_context* c, const rt_camera* cam, int y0, int y1, const char* who, CamPlan& P) {
+  const std::string w = std::string(who) + ": ";
+  if (!c) return fail(RT_E_INVALID, w + "NULL context");
+  if (!c->has_scene) return fail(RT_E_INVALID, w + "no scene set");
+  rt_camera z;
+  std::memset(&z, 0, sizeof z);
+  if (cam) z = *cam;
+  const DevScene& s = c->sc;
+  CamArgs& A = P.A;
+  std::memset(&A, 0, sizeof A);
+  if (z.model < RT_CAMERA_PINHOLE || z.model > RT_CAMERA_THINLENS) return fail(RT_E_INVALID, w + "unknown camera model");
+  if (z.flags & ~RT_CAMERA_POSED) return fail(RT_E_INVALID, w + "unknown flag bits");
+  if (z.samples < 0 || z.samples > RT_CAMERA_MAX_SAMPLES)
+    return fail(RT_E_INVALID, w + "samples outside [0, RT_CAMERA_MAX_SAMPLES]");
+  if (!((z.width == 0 && z.height == 0) || (z.width >= 2 && z.height >= 2)))
+    return fail(RT_E_INVALID, w + "width and height must both be 0 or both be >= 2");
+  A.model = z.model;
+  A.posed = (z.flags & RT_CAMERA_POSED) ? 1 : 0;
+  A.S = z.samples == 0 ? 4 : z.samples;
+  A.D = z.model == RT_CAMERA_THINLENS ? 4 : 2;
+  A.W = z.width ? z.width : s.width;
+  A.H = z.height ? z.height : s.height;
+  if ((long long)A.W * A.H > 2147483647LL) return fail(RT_E_INVALID, w + "the frame has more than 2^31 - 1 pixels");
+  if (z.depth < 0) return fail(RT_E_INVALID, w + "depth outside [0, RT_RADIANCE_MAX_DEPTH]");
+  if (int rc = trace_depth(c, who, z.depth, &P.depth); rc != RT_OK) return rc;
+  if (z.chunk_pixels < 0) return fail(RT_E_INVALID, w + "chunk_pixels < 0");
+  if (y0 < 0 || y1 > A.H || y0 >= y1) return fail(RT_E_INVALID, w + "rows must satisfy 0 <= y0 < y1 <= height");
+  const unsigned int maxoff = (19u * (unsigned int)A.S + (unsigned int)(A.S - 1)) * (unsigned int)A.D;
+  while (A.nbits < CAM_JUMP_BITS && (maxoff >> A.nbits) != 0) A.nbits++;
+  A.W1 = (double)(A.W - 1);
+  A.H1 = (double)(A.H - 1);
+  // the view width
+  if (z.model == RT_CAMERA_ORTHO) {
+    if (!(z.extent > 0.0) || !std::isfinite(z.extent)) return fail(RT_E_INVALID, w + "extent must be > 0 and finite");
+    A.vw = z.extent;
+  } else if (z.model != RT_CAMERA_EQUIRECT && z.fov > 0.0) {
+    const double fovr = z.fov * M_PI / 180.0;  // raytracer.go:601-602, as rt_set_scene
+    double tn;
+    if (!go_tan(fovr / 2.0, tn) || !(tn > 0.0) || !std::isfinite(2.0 / tn))
+      return fail(RT_E_INVALID, w + "fov: its Tan is not a positive finite number");
+    A.vw = 2.0 / tn;
+  } else {
+    if (z.model != RT_CAMERA_EQUIRECT && z.fov != z.fov) return fail(RT_E_INVALID, w + "fov is NaN");
+    A.vw = s.vw;
+  }
+  A.vh = A.vw * ((double)A.H / (double)A.W);  // raytracer.go:603
+  if (z.model == RT_CAMERA_THINLENS) {
+    if (!(z.aperture >= 0.0) || !std::isfinite(z.aperture))
+      return fail(RT_E_INVALID, w + "aperture must be >= 0 and finite");
+    if (!(z.focus > 0.0) || !std::isfinite(z.focus)) return fail(RT_E_INVALID, w + "focus must be > 0 and finite");
+    A.half_ap = z.aperture / 2.0;
+    A.focus = z.focus;
+  }
+  if (A.posed) {
+    if (!cam_finite3(z.eye) || !cam_finite3(z.look_at) || !cam_finite3(z.up))
+      return fail(RT_E_INVALID, w + "eye, look_at and up must be finite");
+    const double g[3] = {z.look_at[0] - z.eye[0], z.look_at[1] - z.eye[1], z.look_at[2] - z.eye[2]};
+    const double gl = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    if (!(gl > 0.0) || !std::isfinite(gl)) return fail(RT_E_INVALID, w + "eye == look_at (or too far apart)");
+    const double f[3] = {g[0] / gl, g[1] / gl, g[2] / gl};
+    const double* u = z.up;
+    const double x[3] = {u[1] * f[2] - u[2] * f[1], u[2] * f[0] - u[0] * f[2], u[0] * f[1] - u[1] * f[0]};
+    const double xl = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    if (!(xl > 0.0) || !std::isfinite(xl)) return fail(RT_E_INVALID, w + "up is parallel to the view direction");
+    const double r[3] = {x[0] / xl, x[1] / xl, x[2] / xl};
+    const double wv[3] = {f[1] * r[2] - f[2] * r[1], f[2] * r[0] - f[0] * r[2], f[0] * r[1] - f[1] * r[0]};
+    for (int k = 0; k < 3; k++) {
+      A.eye[k] = z.eye[k];
+      A.r[k] = r[k];
+      A.w[k] = wv[k];
+      A.f[k] = f[k];
+    }
+  }
+  A.first = y0 * A.W;
+  P.pixels = (long long)A.W * (y1 - y0);
+  P.chunk = std::max(1, CAM_BUF_RECORDS / A.S);
+  if (z.chunk_pixels > 0) P.chunk = std::min(P.chunk, z.chunk_pixels);
+  const long long nch = (P.pixels + P.chunk - 1) / P.chunk;
+  if (nch > 2147483647LL) return fail(RT_E_INVALID, w + "chunk_pixels cuts the band into more than 2^31 - 1 chunks");
+  P.chunks = (int)nch;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_camera_rays_async(rt_context* c, const rt_camera* cam, int y0, int y1, rt_ray* d_rays, void* stream) {
+  const char* who = "rt_camera_rays_async";
+  CamPlan P;
+  if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
+  if (!d_rays) return fail(RT_E_INVALID, std::string(who) + ": NULL ray pointer");
+  if (((uintptr_t)d_rays & 15) != 0) return fail(RT_E_INVALID, std::string(who) + ": ray array must be 16-byte aligned");
+  DeviceGuard guard(c->device);
+  long long n = P.pixels * P.A.S;
+  const long long blocks = (n + WG - 1) / WG;
+  if (blocks > 2147483647LL) return fail(RT_E_INVALID, std::string(who) + ": too many rays for one launch");
+  void* args[] = {(void*)&P.A, (void*)&n, (void*)&d_rays};
+  HIP_TRY(hipLaunchKernel((const void*)cam_rays_kernel, dim3((unsigned)blocks), dim3(WG), args, 0, (hipStream_t)stream));
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+int rt_render_camera_chunks(rt_context* c, const rt_camera* cam, int y0, int y1) {
+  CamPlan P;
+  if (int rc = cam_setup(c, cam, y0, y1, "rt_render_camera_chunks", P); rc != RT_OK) return rc;
+  return P.chunks;
+}
+
+int rt_render_camera_async(rt_context* c, const rt_camera* cam, int y0, int y1, void* d_rgba, double* d_mean,
+                           void* stream) {
+  const char* who = "rt_render_camera_async";
+  CamPlan P;
+  if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
+  if (!d_rgba && !d_mean) return fail(RT_E_INVALID, std::string(who) + ": d_rgba and d_mean are both NULL");
+  if (((uintptr_t)d_rgba & 3) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_rgba must be 4-byte aligned");
+  if (((uintptr_t)d_mean & 7) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_mean must be 8-byte aligned");
+  const DevScene& s = c->sc;
+  DeviceGuard guard(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  int S = P.A.S;
+  // the sample buffer: grown when a call needs more (calls on a context are ordered)
+  const size_t need = (size_t)std::min<long long>(P.pixels, P.chunk) * S * sizeof(rt_radiance);
+  if (need > c->cam_buf_bytes) {
+    if (c->cam_buf) {
+      HIP_TRY(hipDeviceSynchronize());  // an earlier camera render may still use the old one
+      (void)hipFree(c->cam_buf);
+      c->cam_buf = nullptr;
+      c->cam_buf_bytes = 0;
+    }
+    HIP_TRY(hipMalloc((void**)&c->cam_buf, need));
+    c->cam_buf_bytes = need;
+  }
+  const void* kfn = k_camera_kernels[(s.use_bvh ? 1 : 0) | (s.has_csg ? 2 : 0) | (s.num_programs > 0 ? 4 : 0)];
+  const char* blob = s.blob;
+  const rt_radiance* rec = c->cam_buf;
+  uint32_t* rgba = (uint32_t*)d_rgba;
+  double inv = 1.0 / (double)S;
+  for (long long px0 = 0; px0 < P.pixels; px0 += P.chunk) {
+    int npix = (int)std::min<long long>(P.chunk, P.pixels - px0);
+    TraceArgsT<true> Q;
+    std::memset(&Q, 0, sizeof Q);
+    int wgs = 0;
+    if (int rc = trace_prepare(c, npix * S, P.depth, nullptr, c->cam_buf, st, Q, wgs); rc != RT_OK) return rc;
+    Q.cam = P.A;
+    Q.cam.first = P.A.first + (int)px0;
+    void* targs[] = {(void*)&blob, (void*)&Q};
+    HIP_TRY(hipLaunchKernel(kfn, dim3((unsigned)wgs), dim3(WG), targs, 0, st));
+    void* rargs[] = {(void*)&rec, (void*)&npix, (void*)&S, (void*)&inv, (void*)&px0, (void*)&rgba, (void*)&d_mean};
+    HIP_TRY(hipLaunchKernel((const void*)cam_resolve_kernel, dim3((unsigned)((npix + WG - 1) / WG)), dim3(WG), rargs, 0,
+                            st));
+  }
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+}  // extern "C"

@@ -610,6 +610,8 @@ struct rt_context {
   double* trace_ws = nullptr;
   size_t trace_ws_bytes = 0;
   unsigned int* trace_ticket = nullptr;
+  rt_radiance* cam_buf = nullptr;  // camera renders' sample records of one chunk (rt_camera.hip)
+  size_t cam_buf_bytes = 0;
 };
 
 namespace {
@@ -1592,6 +1594,7 @@ void rt_destroy(rt_context* c) {
   (void)hipFree(c->gctl);
   (void)hipFree(c->trace_ws);
   (void)hipFree(c->trace_ticket);
+  (void)hipFree(c->cam_buf);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   delete c;
@@ -2822,4 +2825,5 @@ int rt_debug_run_surface(rt_context* c, int program, int n, const long long* fac
 #include "rt_ssim.hip"
 #include "rt_query.hip"
 #include "rt_trace.hip"
+#include "rt_camera.hip"
 #include "rt_render_api.hip"

@@ -62,14 +62,22 @@ struct BoolC {
   static constexpr bool value = B;
 };
 
+// The kernel's argument record. GEN (camera renders, rt_camera.hip): the
+// specialisation for true, defined there, adds the camera the lanes form their
+// rays from; without GEN this is TraceArgs itself.
+template <bool GEN>
+struct TraceArgsT : TraceArgs {};
+
 struct __attribute__((aligned(16))) R16 {
   double z;
   int object, rays;
 };
 
 // VM: the scene has closure surfaces (run_vm's register file lives in scratch)
-template <bool BVH, bool CSG, bool VM>
-__global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict__ blob, TraceArgs Q) {
+// GEN: ticket t is sample t % S of the launch's pixel t / S and the lane forms
+// that ray itself (cam_ticket_ray, rt_camera.hip) instead of loading Q.rays[t]
+template <bool BVH, bool CSG, bool VM, bool GEN>
+__global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict__ blob, TraceArgsT<GEN> Q) {
   __shared__ uint64_t s_mask[BVH ? WAVES_PER_WG * BVH_STACK : 1];
   __shared__ int s_ref[BVH ? WAVES_PER_WG * BVH_STACK : 1];
   const int lane = (int)(threadIdx.x & 63);
@@ -278,13 +286,19 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
         if (base + cnt >= (unsigned int)Q.n) drained = true;
         const unsigned int mine = base + (unsigned int)__popcll(im & ((1ull << lane) - 1ull));
         if (!act && base < (unsigned int)Q.n && mine < (unsigned int)Q.n) {
-          // the lane's ray: four 16-byte loads of its 64-byte record
-          const Q16* rp = reinterpret_cast<const Q16*>(Q.rays + mine);
-          const Q16 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
-          ray.o = mk(r0.a, r0.b, r1.a);
-          ray.d = mk(r1.b, r2.a, r2.b);
-          tmax = r3.a;
-          excl = __double2loint(r3.b);
+          if constexpr (GEN) {
+            cam_ticket_ray(Q.cam, mine, ray.o, ray.d);
+            tmax = __builtin_inf();
+            excl = -1;
+          } else {
+            // the lane's ray: four 16-byte loads of its 64-byte record
+            const Q16* rp = reinterpret_cast<const Q16*>(Q.rays + mine);
+            const Q16 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
+            ray.o = mk(r0.a, r0.b, r1.a);
+            ray.d = mk(r1.b, r2.a, r2.b);
+            tmax = r3.a;
+            excl = __double2loint(r3.b);
+          }
           idx = (int)mine;
           sp = 0;
           nrays = 1;
@@ -618,10 +632,10 @@ __global__ __launch_bounds__(WG) void rt_camera_rays_kernel(const char* __restri
 
 // [BVH | CSG << 1 | VM << 2]
 const void* const k_trace_kernels[8] = {
-    (const void*)rt_trace_kernel<false, false, false>, (const void*)rt_trace_kernel<true, false, false>,
-    (const void*)rt_trace_kernel<false, true, false>,  (const void*)rt_trace_kernel<true, true, false>,
-    (const void*)rt_trace_kernel<false, false, true>,  (const void*)rt_trace_kernel<true, false, true>,
-    (const void*)rt_trace_kernel<false, true, true>,   (const void*)rt_trace_kernel<true, true, true>};
+    (const void*)rt_trace_kernel<false, false, false, false>, (const void*)rt_trace_kernel<true, false, false, false>,
+    (const void*)rt_trace_kernel<false, true, false, false>,  (const void*)rt_trace_kernel<true, true, false, false>,
+    (const void*)rt_trace_kernel<false, false, true, false>,  (const void*)rt_trace_kernel<true, false, true, false>,
+    (const void*)rt_trace_kernel<false, true, true, false>,   (const void*)rt_trace_kernel<true, true, true, false>};
 
 // Workgroups of the persistent grid for a call at `depth`: TR_WG_PER_CU per CU,
 // fewer when depth - 1 frames for that many lanes would exceed TR_WS_MAX.
@@ -640,25 +654,13 @@ int trace_depth(const rt_context* c, const char* who, int depth, int* out) {
   return RT_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rt_query_radiance_async(rt_context* c, int n, const rt_ray* d_rays, int depth, rt_radiance* d_out, void* stream) {
-  const char* who = "rt_query_radiance_async";
-  if (!c) return fail(RT_E_INVALID, std::string(who) + ": NULL context");
-  if (!c->has_scene) return fail(RT_E_INVALID, std::string(who) + ": no scene set");
-  if (n < 0) return fail(RT_E_INVALID, std::string(who) + ": n < 0");
-  int D = 0;
-  if (int rc = trace_depth(c, who, depth, &D); rc != RT_OK) return rc;
-  if (n == 0) return RT_OK;
-  if (!d_rays || !d_out) return fail(RT_E_INVALID, std::string(who) + ": NULL ray or output pointer");
-  if (((uintptr_t)d_rays & 15) != 0 || ((uintptr_t)d_out & 15) != 0)
-    return fail(RT_E_INVALID, std::string(who) + ": ray and radiance arrays must be 16-byte aligned");
+// What a launch of n tickets at depth D needs before it: the grid, the frame
+// stack (grown when a call needs more: calls on a context are ordered), the
+// zeroed ticket and the argument record (zero-filled by the caller).
+int trace_prepare(rt_context* c, int n, int D, const rt_ray* d_rays, rt_radiance* d_out, hipStream_t stream,
+                  TraceArgs& Q, int& wgs_out) {
   const DevScene& s = c->sc;
-  DeviceGuard guard(c->device);
   const int wgs = std::min(trace_grid_wgs(c, D), (n + WG - 1) / WG);
-  // the workspace: grown when a call needs more (calls on a context are ordered)
   const size_t need = (size_t)std::max(1, D - 1) * TR_FIELDS * sizeof(double) * WG * (size_t)wgs;
   if (need > c->trace_ws_bytes) {
     if (c->trace_ws) {
@@ -671,9 +673,7 @@ int rt_query_radiance_async(rt_context* c, int n, const rt_ray* d_rays, int dept
     c->trace_ws_bytes = need;
   }
   if (!c->trace_ticket) HIP_TRY(hipMalloc((void**)&c->trace_ticket, 64));
-  HIP_TRY(hipMemsetAsync(c->trace_ticket, 0, sizeof(unsigned int), (hipStream_t)stream));
-  TraceArgs Q;
-  std::memset(&Q, 0, sizeof Q);
+  HIP_TRY(hipMemsetAsync(c->trace_ticket, 0, sizeof(unsigned int), stream));
   Q.rays = d_rays;
   Q.out = d_out;
   Q.ticket = c->trace_ticket;
@@ -703,6 +703,31 @@ int rt_query_radiance_async(rt_context* c, int n, const rt_ray* d_rays, int dept
       Q.bvh_hi[k] = s.bvh_hi[k];
     }
   }
+  wgs_out = wgs;
+  return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_query_radiance_async(rt_context* c, int n, const rt_ray* d_rays, int depth, rt_radiance* d_out, void* stream) {
+  const char* who = "rt_query_radiance_async";
+  if (!c) return fail(RT_E_INVALID, std::string(who) + ": NULL context");
+  if (!c->has_scene) return fail(RT_E_INVALID, std::string(who) + ": no scene set");
+  if (n < 0) return fail(RT_E_INVALID, std::string(who) + ": n < 0");
+  int D = 0;
+  if (int rc = trace_depth(c, who, depth, &D); rc != RT_OK) return rc;
+  if (n == 0) return RT_OK;
+  if (!d_rays || !d_out) return fail(RT_E_INVALID, std::string(who) + ": NULL ray or output pointer");
+  if (((uintptr_t)d_rays & 15) != 0 || ((uintptr_t)d_out & 15) != 0)
+    return fail(RT_E_INVALID, std::string(who) + ": ray and radiance arrays must be 16-byte aligned");
+  const DevScene& s = c->sc;
+  DeviceGuard guard(c->device);
+  TraceArgs Q;
+  std::memset(&Q, 0, sizeof Q);
+  int wgs = 0;
+  if (int rc = trace_prepare(c, n, D, d_rays, d_out, (hipStream_t)stream, Q, wgs); rc != RT_OK) return rc;
   const char* blob = s.blob;
   void* args[] = {(void*)&blob, (void*)&Q};
   const void* kfn = k_trace_kernels[(s.use_bvh ? 1 : 0) | (s.has_csg ? 2 : 0) | (s.num_programs > 0 ? 4 : 0)];

@@ -101,6 +101,12 @@ def load_library(path=None):
     l.rt_query_radiance_lanes.restype = i
     l.rt_query_camera_rays_async.argtypes = [vp, i, i, vp, vp]
     l.rt_query_camera_rays_async.restype = i
+    l.rt_camera_rays_async.argtypes = [vp, vp, i, i, vp, vp]
+    l.rt_camera_rays_async.restype = i
+    l.rt_render_camera_async.argtypes = [vp, vp, i, i, vp, vp, vp]
+    l.rt_render_camera_async.restype = i
+    l.rt_render_camera_chunks.argtypes = [vp, vp, i, i]
+    l.rt_render_camera_chunks.restype = i
     if l.rt_abi_version() != abi.RT_ABI_VERSION:
         raise RenderError("librtamd ABI version mismatch")
     _lib = l
@@ -421,6 +427,112 @@ class RenderContext:
         self.camera_rays_async(y0, y1, out)
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy().view(abi.RAY_DTYPE).reshape(rows, w, 4)
+
+    # ---- camera renders (include/rt_abi.h rt_camera, rt_render_camera_async) ----
+    @staticmethod
+    def camera(model="pinhole", samples=0, size=None, depth=0, chunk_pixels=0, fov=0.0, extent=0.0, aperture=0.0,
+               focus=0.0, eye=None, look_at=None, up=None):
+        """An abi.rt_camera. No arguments: the scene's own camera at 4 samples
+        (Render()). `model` a name of abi.CAMERA_MODELS or an RT_CAMERA_*
+        value; `size` (width, height); giving any of eye / look_at / up poses
+        the camera (defaults: the reference's eye (0, 0, -1) looking at the
+        origin, up (0, 1, 0))."""
+        cam = abi.rt_camera()
+        cam.model = abi.CAMERA_MODELS[model] if isinstance(model, str) else int(model)
+        cam.samples = int(samples)
+        if size is not None:
+            cam.width, cam.height = int(size[0]), int(size[1])
+        cam.depth = int(depth)
+        cam.chunk_pixels = int(chunk_pixels)
+        cam.fov, cam.extent, cam.aperture, cam.focus = float(fov), float(extent), float(aperture), float(focus)
+        if eye is not None or look_at is not None or up is not None:
+            cam.flags = abi.RT_CAMERA_POSED
+            cam.eye[:] = [float(v) for v in ((0.0, 0.0, -1.0) if eye is None else eye)]
+            cam.look_at[:] = [float(v) for v in ((0.0, 0.0, 0.0) if look_at is None else look_at)]
+            cam.up[:] = [float(v) for v in ((0.0, 1.0, 0.0) if up is None else up)]
+        return cam
+
+    def _camera_frame(self, cam):
+        """(cam or the zero camera, W, H, samples) of a camera render."""
+        cam = abi.rt_camera() if cam is None else cam
+        w = int(cam.width) or self.packed.width
+        h = int(cam.height) or self.packed.height
+        return cam, w, h, int(cam.samples) or 4
+
+    def _camera_out(self, t, nbytes, what, name):
+        assert t.is_cuda and t.is_contiguous(), "%s: %s must be a contiguous CUDA tensor" % (what, name)
+        assert t.device.index == self.device, "%s: %s is on another device" % (what, name)
+        assert t.numel() * t.element_size() == nbytes, "%s: %s must hold %d bytes" % (what, name, nbytes)
+        return C.c_void_p(t.data_ptr())
+
+    def camera_rays_ex_async(self, cam, y0, y1, out, stream=None):
+        """Enqueue the rays of camera `cam` (None: the zero camera) for rows
+        [y0, y1) of its frame: `out` a uint8 CUDA tensor of (y1 - y0) * W *
+        samples records of 64 bytes (abi.RAY_DTYPE), in [row][x][sample] order."""
+        cam, w, _, S = self._camera_frame(cam)
+        rows = max(0, int(y1) - int(y0))
+        assert out.dtype == self.torch.uint8, "camera_rays_ex_async: out must be a uint8 tensor"
+        ptr = self._camera_out(out, rows * w * S * abi.RAY_DTYPE.itemsize, "camera_rays_ex_async", "out")
+        s = self.torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_camera_rays_async(self.handle, C.byref(cam), int(y0), int(y1), ptr,
+                                             C.c_void_p(s.cuda_stream)), "rt_camera_rays_async")
+
+    def camera_rays_ex(self, cam=None, y0=0, y1=None):
+        """Synchronous rays of camera `cam` for rows [y0, y1) -> numpy
+        abi.RAY_DTYPE array [rows, W, samples]."""
+        torch = self.torch
+        cam, w, h, S = self._camera_frame(cam)
+        if y1 is None:
+            y1 = h
+        rows = max(0, y1 - y0)
+        out = torch.empty(rows * w * S * abi.RAY_DTYPE.itemsize, dtype=torch.uint8, device="cuda:%d" % self.device)
+        self.camera_rays_ex_async(cam, y0, y1, out)
+        torch.cuda.synchronize(self.device)
+        return out.cpu().numpy().view(abi.RAY_DTYPE).reshape(rows, w, S)
+
+    def render_camera_async(self, cam, y0, y1, rgba=None, mean=None, stream=None):
+        """Enqueue the camera render of rows [y0, y1) of `cam`'s frame (None:
+        the zero camera, Render()'s pixels) into either or both of `rgba`, a
+        uint8 CUDA tensor [rows, W, 4], and `mean`, a float64 CUDA tensor
+        [rows, W, 3] (the mean radiance before quantisation). Camera renders
+        and radiance queries on one context share a workspace: keep them
+        ordered with respect to each other."""
+        torch = self.torch
+        cam, w, _, _ = self._camera_frame(cam)
+        rows = max(0, int(y1) - int(y0))
+        rp = mp = None
+        if rgba is not None:
+            assert rgba.dtype == torch.uint8, "render_camera_async: rgba must be a uint8 tensor"
+            rp = self._camera_out(rgba, rows * w * 4, "render_camera_async", "rgba")
+        if mean is not None:
+            assert mean.dtype == torch.float64, "render_camera_async: mean must be a float64 tensor"
+            mp = self._camera_out(mean, rows * w * 24, "render_camera_async", "mean")
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_render_camera_async(self.handle, C.byref(cam), int(y0), int(y1), rp, mp,
+                                               C.c_void_p(s.cuda_stream)), "rt_render_camera_async")
+
+    def render_camera(self, cam=None, y0=0, y1=None, mean=False):
+        """Synchronous camera render of rows [y0, y1) -> numpy uint8 [rows, W,
+        4]; with mean=True -> (that, float64 [rows, W, 3] mean radiance)."""
+        torch = self.torch
+        cam, w, h, _ = self._camera_frame(cam)
+        if y1 is None:
+            y1 = h
+        rows = max(0, y1 - y0)
+        dev = "cuda:%d" % self.device
+        rgba = torch.empty((rows, w, 4), dtype=torch.uint8, device=dev)
+        m = torch.empty((rows, w, 3), dtype=torch.float64, device=dev) if mean else None
+        self.render_camera_async(cam, y0, y1, rgba, m)
+        torch.cuda.synchronize(self.device)
+        return (rgba.cpu().numpy(), m.cpu().numpy()) if mean else rgba.cpu().numpy()
+
+    def render_camera_chunks(self, cam=None, y0=0, y1=None):
+        """Launches of the radiance kernel render_camera_async makes for these arguments."""
+        cam, _, h, _ = self._camera_frame(cam)
+        n = self.lib.rt_render_camera_chunks(self.handle, C.byref(cam), int(y0), int(h if y1 is None else y1))
+        if n < 0:
+            _check(n, "rt_render_camera_chunks")
+        return n
 
     def image_from_radiance(self, out, samples):
         """Average `samples` consecutive radiance records per pixel and quantise

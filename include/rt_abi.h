@@ -572,6 +572,105 @@ int rt_query_radiance_lanes(rt_context *ctx, int depth);
  * effects on the context. */
 int rt_query_camera_rays_async(rt_context *ctx, int y0, int y1, rt_ray *d_rays, void *stream);
 
+/* ---- Camera renders: any sample count and camera model, fused on the device ----
+ * The radiance kernel forms the camera's rays itself (no ray array), writes
+ * one rt_radiance record per sample into a bounded context-owned buffer, and a
+ * resolve kernel averages and quantises them (csrc/rt_camera.hip). All zero =
+ * the scene's own camera at 4 samples: Render()'s pixels, byte for byte.
+ *
+ * Everything is FP64, one rounding per operation, in the order written here.
+ * Draws: pixel (x, y) uses Render()'s stream PCG(0xDEAD ^ x, 0xBEEF ^ ymin),
+ * ymin = 20 * (y / 20) (raytracer.go:627-634). With S samples and D draws per
+ * sample (4 for the thin lens, else 2) a row consumes S * D draws; sample s of
+ * row y reads draws (y - ymin) * S * D + s * D + 0 .. D-1 -- what the
+ * reference would draw if numSamples were S.
+ * Screen: dx = draw0 - 0.5, dy = draw1 - 0.5, su = (x + dx) / (W - 1),
+ * sv = (y + dy) / (H - 1); with vw the view width and
+ * vh = vw * (float(H) / float(W)): u = su * vw - vw / 2, v = sv * vh - vh / 2
+ * (raytracer.go:603, 644-647).
+ * Camera space is the reference's: eye e = (0, 0, -1), screen plane z = 0,
+ * x right, y up, looking along +z.
+ *   RT_CAMERA_PINHOLE   vw = 2 / Tan(fov * Pi / 180 / 2) (raytracer.go:601-602;
+ *                       fov <= 0: the scene's vw); o = (u, -v, 0),
+ *                       d = normalize(o - e)
+ *   RT_CAMERA_ORTHO     vw = extent; o = (u, -v, 0), d = (0, 0, 1)
+ *   RT_CAMERA_EQUIRECT  theta = (su - 0.5) * 360, phi = (0.5 - sv) * 180;
+ *                       o = e, d = (Sin theta * Cos phi, Sin phi,
+ *                       Cos theta * Cos phi), Sin / Cos being Go's math.Sin /
+ *                       math.Cos of 0.017453292519943295 * angle (RT_VM_SIN)
+ *   RT_CAMERA_THINLENS  the pinhole's o and d; P = e + d * (focus / d.z);
+ *                       rho = (aperture / 2) * sqrt(draw2), alpha = 360 * draw3;
+ *                       L = e + (rho * Cos alpha, rho * Sin alpha, 0); the ray
+ *                       is (L, normalize(P - L))
+ * Pose (RT_CAMERA_POSED; without it camera space is world space):
+ * f = normalize(look_at - eye), r = normalize(cross(up, f)), w = cross(f, r);
+ * a camera-space point p maps to eye + p.x * r + p.y * w + (p.z + 1) * f, a
+ * direction to d.x * r + d.y * w + d.z * f (not renormalised), terms added
+ * left to right.
+ * Pixel: mean = ((c0 + c1) + c2 + ...) * (1.0 / S) in sample order, each byte
+ * uint8(uint32(mean * 65535) >> 8) as Go converts on amd64 (vec.go:104-107). */
+#define RT_CAMERA_PINHOLE  0   /* the reference's camera model (raytracer.go:601-652) */
+#define RT_CAMERA_ORTHO    1
+#define RT_CAMERA_EQUIRECT 2   /* 360 x 180 degree panorama */
+#define RT_CAMERA_THINLENS 3   /* pinhole with a finite aperture: depth of field */
+#define RT_CAMERA_POSED    1   /* flags: eye / look_at / up are given */
+#define RT_CAMERA_MAX_SAMPLES 1024
+
+typedef struct rt_camera {      /* all zero = the scene's own camera, 4 samples: Render() */
+    int32_t model, flags;
+    int32_t samples;            /* per pixel, 1..RT_CAMERA_MAX_SAMPLES; 0: 4 */
+    int32_t width, height;      /* both 0: the scene's; else both >= 2 */
+    int32_t depth;              /* 0: the scene's; else 1..RT_RADIANCE_MAX_DEPTH */
+    int32_t chunk_pixels;       /* 0: automatic (below); > 0: at most this many pixels per launch */
+    int32_t reserved;
+    double  fov;                /* degrees; <= 0: the scene's (pinhole, thin lens) */
+    double  extent;             /* ortho: world width of the view, > 0 */
+    double  aperture, focus;    /* thin lens: lens diameter >= 0, focal-plane distance > 0 */
+    double  eye[3], look_at[3], up[3];   /* RT_CAMERA_POSED only */
+} rt_camera;
+
+/* The camera's rays for rows [y0, y1) of its frame (W x H: the camera's size,
+ * else the scene's): samples * W * (y1 - y0) records in [row][x][sample]
+ * order with tmax = +inf, exclude = -1, reserved = 0. cam == NULL means all
+ * zeros, for which these are exactly the records of
+ * rt_query_camera_rays_async. RT_E_INVALID (with an rt_last_error text): NULL
+ * context, no scene set, unknown model or flag bits, samples / width / height
+ * / depth / chunk_pixels out of range (a frame of more than 2^31 - 1 pixels
+ * included), rows outside 0 <= y0 < y1 <= H, a fov whose Tan is not a positive
+ * finite number, extent (ortho), focus or aperture (thin lens) out of range
+ * or not finite, a posed camera with eye == look_at or up parallel to the view
+ * direction (or not finite), NULL or not 16-byte aligned d_rays. Ordered on
+ * `stream`; no side effects on the context. */
+int rt_camera_rays_async(rt_context *ctx, const rt_camera *cam, int y0, int y1, rt_ray *d_rays, void *stream);
+
+/* Render rows [y0, y1) of the camera's frame into either or both of d_rgba
+ * (row y0 first, stride 4 * W, alpha 255) and d_mean (3 doubles per pixel,
+ * 8-byte aligned: the mean before quantisation); not both NULL. Device
+ * pointers only. Errors as rt_camera_rays_async, for the output pointers:
+ * both NULL, d_mean not 8-byte aligned, d_rgba not 4-byte aligned (pixels are
+ * stored as 32-bit words).
+ * The band's pixels, in [row][x] order, are cut into chunks of
+ * max(1, 2097152 / samples) consecutive pixels (chunk_pixels if that is
+ * smaller; chunks need not align to rows). Per chunk the call enqueues on
+ * `stream`: the ticket counter's reset, one launch of the radiance kernel in
+ * which ticket t is sample t % samples of the chunk's pixel t / samples, and
+ * one resolve launch (a thread per pixel). The host never waits between
+ * chunks. The sample records live in a context-owned buffer of at most 64 MiB,
+ * allocated at the first call, grown when a call needs more (which waits for
+ * the device) and freed by rt_destroy.
+ * The call touches neither the frame counters (rt_read_stats) nor the tile
+ * order, the specialisation state or pending compiles, and the pixels do not
+ * depend on rt_set_accel. It uses the radiance queries' workspace and ticket
+ * and its own sample buffer: camera renders and radiance queries on one
+ * context must be ordered with respect to each other -- one stream, or events
+ * between streams. */
+int rt_render_camera_async(rt_context *ctx, const rt_camera *cam, int y0, int y1,
+                           void *d_rgba, double *d_mean, void *stream);
+
+/* Chunks (radiance-kernel launches) rt_render_camera_async makes for these
+ * arguments; negative: the RT_E_INVALID it would return (buffers aside). */
+int rt_render_camera_chunks(rt_context *ctx, const rt_camera *cam, int y0, int y1);
+
 /* SSIM of two RGBA8 frames in device memory (width x height, stride 4W), the
  * reference's parity metric prim.SSIM (internal/prim/ssim.go:27-182; used by
  * raytracer_test.go:42 with threshold 0.99). Synchronous on `stream`.

@@ -18,7 +18,16 @@ rt_render_rows_async for the same frame on the same context (specialisation
 off: the generic megakernel, which traces the same rays) and the ratio of the
 two. Device events around 5 launches after 1 warm-up.
 
-usage: python scripts/query_rate.py [--configs c3,c4csg,c5] [--modes closest,occluded,radiance] [--out FILE]
+Camera mode (not in the default modes; writes profiles/camera/camera_rate.jsonl
+unless --out says otherwise): the zero camera at 1920x1080 x 4 samples through
+rt_render_camera_async (fused: no ray array, chunked sample buffer, resolve
+kernel) beside the three-step route it replaces -- camera_rays_async +
+query_radiance_async + image_from_radiance -- three runs each of device
+events around 5 frames after 1 warm-up, with the times of each chunk's trace +
+resolve, and beside rt_render_rows_async generic and specialised. On c3 also
+S = 1, 4, 16, 64. Every line asserts that the fused bytes equal render()'s.
+
+usage: python scripts/query_rate.py [--configs c3,c4csg,c5] [--modes closest,occluded,radiance,camera] [--out FILE]
 """
 import argparse
 import json
@@ -72,6 +81,74 @@ def radiance_line(torch, abi, ctx, name, seed):
             "image_equals_render": same, "launches": RAD_LAUNCHES, "warmup": RAD_WARMUP, "seed": seed}
 
 
+def camera_line(torch, abi, ctx, name, seed):
+    """The fused camera render of the zero camera beside the three-step route
+    and the megakernel; on c3 also other sample counts."""
+    img = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0")
+    fused = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0")
+    ctx.set_specialize(False)
+    ctx.render_rows_async(0, H, img)
+    zero = ctx.camera()
+    fused_ms = [timed(torch, lambda: ctx.render_camera_async(zero, 0, H, rgba=fused), RAD_WARMUP, RAD_LAUNCHES)
+                for _ in range(3)]
+    torch.cuda.synchronize()
+    same = bool(torch.equal(fused, img))
+    assert same, "%s: the fused zero-camera frame differs from render()" % name
+    chunks = ctx.render_camera_chunks(zero)
+    # the rows that cover each chunk, rendered on their own (one chunk each), to show the tails
+    cpix = 2097152 // 4  # pixels per chunk at 4 samples (include/rt_abi.h)
+    chunk_ms = []
+    for k in range(chunks):
+        y0 = (k * cpix) // W
+        y1 = min(H, -(-((k + 1) * cpix) // W))
+        band = torch.empty((y1 - y0, W, 4), dtype=torch.uint8, device="cuda:0")
+        chunk_ms.append(round(timed(torch, lambda: ctx.render_camera_async(zero, y0, y1, rgba=band), RAD_WARMUP,
+                                    RAD_LAUNCHES), 4))
+        del band
+    n = W * H * 4
+    rays = torch.empty(n * abi.RAY_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+    out = torch.empty(n * abi.RADIANCE_DTYPE.itemsize, dtype=torch.uint8, device="cuda:0")
+    res = {}
+
+    def three_step():
+        ctx.camera_rays_async(0, H, rays)
+        ctx.query_radiance_async(rays, out)
+        res["img"] = ctx.image_from_radiance(out, 4)
+
+    route_ms = [timed(torch, three_step, RAD_WARMUP, RAD_LAUNCHES) for _ in range(3)]
+    route_same = bool(torch.equal(res["img"], img))
+    traced = int(out.view(torch.int32).view(n, 8)[:, 7].sum(dtype=torch.int64).item())
+    del rays, out, res
+    generic_ms = timed(torch, lambda: ctx.render_rows_async(0, H, img), RAD_WARMUP, RAD_LAUNCHES)
+    ctx.set_specialize(True)
+    ctx.render_rows_async(0, H, img)
+    torch.cuda.synchronize()
+    spec_on = bool(ctx.specialized()[0])
+    spec_ms = timed(torch, lambda: ctx.render_rows_async(0, H, img), RAD_WARMUP, RAD_LAUNCHES)
+    ctx.set_specialize(False)
+    fm, rm = min(fused_ms), min(route_ms)
+    line = {"metric": "camera_rate", "config": name, "mode": "camera", "width": W, "height": H, "samples": 4,
+            "depth": int(ctx.packed.scene.depth), "objects": int(ctx.packed.scene.num_objects),
+            "bvh": bool(ctx.scene_info() & abi.RT_INFO_BVH), "chunks": chunks, "rays_traced": traced,
+            "fused_ms": [round(v, 4) for v in fused_ms], "route_ms": [round(v, 4) for v in route_ms],
+            "route_spread_ms": round(max(route_ms) - min(route_ms), 4),
+            "fused_over_route": round(fm / rm, 4), "chunk_rows_ms": chunk_ms,
+            "value": round(traced / fm / 1e3, 2), "unit": "Mrays/s",
+            "render_generic_ms": round(generic_ms, 4), "render_specialized_ms": round(spec_ms, 4),
+            "render_specialized": spec_on, "generic_over_fused": round(generic_ms / fm, 4),
+            "specialized_over_fused": round(spec_ms / fm, 4), "fused_equals_render": same,
+            "route_equals_render": route_same, "launches": RAD_LAUNCHES, "warmup": RAD_WARMUP, "runs": 3, "seed": seed}
+    if name == "c3":
+        sweep = []
+        for S in (1, 4, 16, 64):
+            cam = ctx.camera(samples=S)
+            ms = timed(torch, lambda: ctx.render_camera_async(cam, 0, H, rgba=fused), RAD_WARMUP, RAD_LAUNCHES)
+            sweep.append({"samples": S, "ms": round(ms, 4), "chunks": ctx.render_camera_chunks(cam),
+                          "primary_Mrays_per_s": round(W * H * S / ms / 1e3, 2)})
+        line["samples_sweep"] = sweep
+    return line
+
+
 def camera_rays(fov_deg, seed):
     g = np.random.default_rng(seed)
     vw = 2.0 * math.tan(math.radians(fov_deg) / 2.0)
@@ -123,11 +200,19 @@ def main():
                           "hits" if mode == "closest" else "occluded": answered, "launches": LAUNCHES,
                           "warmup": WARMUP, "seed": args.seed})
             print(json.dumps(lines[-1]), flush=True)
+        del hits, occ
         if "radiance" in modes:
-            del hits, occ
             lines.append(radiance_line(torch, abi, ctx, name, args.seed))
             print(json.dumps(lines[-1]), flush=True)
+        if "camera" in modes:
+            lines.append(camera_line(torch, abi, ctx, name, args.seed))
+            print(json.dumps(lines[-1]), flush=True)
     ctx.close()
+    if args.out is None and "camera" in args.modes.split(","):
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "camera",
+                                "camera_rate.jsonl")
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        lines = [ln for ln in lines if ln["mode"] == "camera"]
     if args.out:
         with open(args.out, "a") as f:
             for ln in lines:
