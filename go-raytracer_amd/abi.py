@@ -248,6 +248,15 @@ class rt_camera(C.Structure):
         ("up", C.c_double * 3),
     ]
 
+
+class rt_adaptive(C.Structure):
+    """An adaptive camera render's stopping rule (rt_render_camera_adaptive_async)."""
+    _fields_ = [
+        ("min_samples", C.c_int32),   # 0: min(4, samples); else 2 <= min_samples <= samples
+        ("reserved", C.c_int32),      # must be 0
+        ("tolerance", C.c_double),    # >= 0, not NaN; +inf: every pixel stops at min_samples
+    ]
+
 # numpy structured dtypes of the same layout as rt_ray / rt_hit / rt_radiance
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("tmax", "<f8"), ("exclude", "<i4"),
                       ("reserved", "<i4")])

@@ -1,5 +1,6 @@
 // rt_camera.hip -- camera renders (include/rt_abi.h rt_camera,
-// rt_camera_rays_async, rt_render_camera_async, rt_render_camera_chunks).
+// rt_camera_rays_async, rt_render_camera_async, rt_render_camera_chunks,
+// rt_render_camera_adaptive_async, rt_render_camera_adaptive_plan).
 //
 // The radiance kernel of rt_trace.hip with a ray source of its own, plus a
 // resolve step. rt_trace_kernel<.., GEN = true> hands out tickets exactly as a
@@ -25,6 +26,18 @@
 // waves share: a wave's loop ends when its lanes hold no ray and every ticket
 // has been handed out, each ray tree is bounded by the depth, and no wave
 // waits for another -- nothing can hang, as for the radiance queries.
+//
+// Adaptive renders (rt_render_camera_adaptive_async): per-pixel sample counts
+// chosen on the device. Passes double the samples of the pixels still active;
+// per chunk and pass one launch of rt_trace_kernel<.., GEN, ADP> -- ticket t is
+// sample s0 + t % b of the pass's list entry t / b, and the number of entries
+// is read from device memory (cam_ticket_limit), so the host enqueues every
+// pass without knowing how many pixels are active -- and one cam_adapt_kernel
+// launch, which continues the pixels' sums, applies the stopping rule, writes
+// the final pixels and lists the others for the next pass. The ADP flag keeps
+// this refill out of the fixed render's instantiations, whose registers have
+// no room for it (DESIGN.md "Adaptive camera renders"). An empty pass drains
+// at the first refill; nothing can hang, by the argument above.
 //
 // PCG position: sample s of row y starts ((y mod 20) * S + s) * D draws into
 // its column's strip stream (D draws per sample), at most 81 916 < 2^17. The
@@ -73,6 +86,11 @@ struct CamArgs {
   double vw, vh;
   double half_ap, focus;               // thin lens: aperture / 2, focal-plane distance
   double eye[3], r[3], w[3], f[3];     // posed: the eye and the basis (right, up, forward)
+  // a pass of an adaptive render (the ADP instantiations; a fixed render reads none of these):
+  // ticket t is sample s0 + t % b of pixel first + (list ? list[t / b] : t / b)
+  int s0, b;
+  const int* list;            // a pass of an adaptive render: its active pixels, relative to `first`
+  const unsigned int* count;  // ... and how many there are (device memory, written by the pass before)
 };
 
 template <>
@@ -136,9 +154,27 @@ __device__ __forceinline__ void cam_ray(const CamArgs& A, int pixel, int s, d3& 
 }
 
 // Ticket t of a GEN launch (t < n <= CAM_BUF_RECORDS)
-__device__ __forceinline__ void cam_ticket_ray(const CamArgs& A, unsigned int t, d3& ro, d3& rd) {
+__device__ __forceinline__ void cam_ticket_ray(const CamArgs& A, unsigned int t, BoolC<false>, d3& ro, d3& rd) {
   const unsigned int p = t / (unsigned int)A.S;
   cam_ray(A, A.first + (int)p, (int)(t - p * (unsigned int)A.S), ro, rd);
+}
+
+// ... of a pass of an adaptive render (the ADP instantiations). One
+// wave-uniform branch on the list pointer: pass 0 has no list.
+__device__ __forceinline__ void cam_ticket_ray(const CamArgs& A, unsigned int t, BoolC<true>, d3& ro, d3& rd) {
+  const unsigned int p = t / (unsigned int)A.b;
+  int pixel = (int)p;
+  if (A.list) pixel = A.list[p];
+  cam_ray(A, A.first + pixel, A.s0 + (int)(t - p * (unsigned int)A.b), ro, rd);
+}
+
+// Tickets of an ADP launch of at most n = pixels * b: min(*count, pixels) * b
+// when the launch has a count, read once per wave. The clamp keeps a ticket
+// inside the chunk's sample buffer and list whatever the count holds.
+__device__ __forceinline__ unsigned int cam_ticket_limit(const CamArgs& A, unsigned int n) {
+  if (!A.count) return n;
+  const unsigned long long m = (unsigned long long)*A.count * (unsigned int)A.b;
+  return m < (unsigned long long)n ? (unsigned int)m : n;
 }
 
 // rt_camera_rays_async: one thread per (pixel, sample) of the band
@@ -187,12 +223,117 @@ __global__ __launch_bounds__(WG) void cam_resolve_kernel(const rt_radiance* __re
   }
 }
 
+// One pass of an adaptive render (include/rt_abi.h "Adaptive camera renders").
+struct AdaptArgs {
+  const rt_radiance* rec;      // the pass's records: entry j's b samples at rec[j * b ..]
+  int npix;                    // pixels of the chunk
+  int b, n, S;                 // the pass's batch, samples per active pixel after it, the cap
+  double tol2;
+  const int* list;             // the pass's active pixels (NULL: pass 0, entry j is pixel j)
+  const unsigned int* count;   // ... and their number (NULL: npix)
+  int* next;                   // the next pass's list and count (unused when n == S)
+  unsigned int* next_count;
+  double* state;               // [6][npix]: sum r g b, sum of squares r g b
+  long long px0;               // the chunk's first pixel relative to the band
+  uint32_t* rgba;
+  double* mean;
+  int32_t* samples;
+};
+
+// One thread per active list entry: the entry's b records added to the pixel's
+// running sums in sample order, then the stopping rule. A pixel that is
+// converged, or holds S samples, is written out; any other goes to the next
+// pass's list (one atomic per wave, rank by popcount; the order of a list does
+// not matter to any output).
+__global__ __launch_bounds__(WG) void cam_adapt_kernel(AdaptArgs A) {
+  const unsigned int j = blockIdx.x * WG + threadIdx.x;
+  unsigned int lim = (unsigned int)A.npix;
+  if (A.count) {
+    const unsigned int cnt = *A.count;
+    if (cnt < lim) lim = cnt;
+  }
+  bool valid = j < lim;
+  unsigned int p = j;
+  if (valid && A.list) {
+    p = (unsigned int)A.list[j];
+    valid = p < (unsigned int)A.npix;  // (always, for a list this kernel wrote)
+  }
+  bool again = false;
+  if (valid) {
+    const Q16* rp = reinterpret_cast<const Q16*>(A.rec + (size_t)j * A.b);
+    double* st = A.state + p;
+    const size_t np = (size_t)A.npix;
+    d3 sum, sq;
+    int s = 0;
+    if (A.list) {
+      sum = mk(st[0], st[np], st[2 * np]);
+      sq = mk(st[3 * np], st[4 * np], st[5 * np]);
+    } else {
+      const Q16 a = rp[0], b = rp[1];
+      sum = mk(a.a, a.b, b.a);
+      sq = mul(sum, sum);
+      s = 1;
+    }
+    for (; s < A.b; s++) {
+      const Q16 a = rp[2 * s], b = rp[2 * s + 1];
+      const d3 c = mk(a.a, a.b, b.a);
+      sum = add(sum, c);
+      sq = add(sq, mul(c, c));
+    }
+    const double inv = 1.0 / (double)A.n;
+    const d3 m = scale(sum, inv);
+    const d3 v = sub(sq, mul(sum, m));
+    const double den = (double)(A.n * (A.n - 1));
+    const bool conv = v.x / den <= A.tol2 && v.y / den <= A.tol2 && v.z / den <= A.tol2;
+    if (conv || A.n >= A.S) {
+      const long long q = A.px0 + p;
+      if (A.mean) {
+        A.mean[q * 3 + 0] = m.x;
+        A.mean[q * 3 + 1] = m.y;
+        A.mean[q * 3 + 2] = m.z;
+      }
+      if (A.rgba) {
+        const uint32_t r8 = go_f64_to_u32(m.x * 65535.0) >> 8;
+        const uint32_t g8 = go_f64_to_u32(m.y * 65535.0) >> 8;
+        const uint32_t b8 = go_f64_to_u32(m.z * 65535.0) >> 8;
+        A.rgba[q] = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
+      }
+      if (A.samples) A.samples[q] = A.n;
+    } else {
+      st[0] = sum.x;
+      st[np] = sum.y;
+      st[2 * np] = sum.z;
+      st[3 * np] = sq.x;
+      st[4 * np] = sq.y;
+      st[5 * np] = sq.z;
+      again = true;
+    }
+  }
+  const uint64_t am = wave_ballot(again);
+  if (am) {
+    const int lane = (int)(threadIdx.x & 63);
+    const int first = __builtin_amdgcn_readfirstlane(__builtin_ctzll(am));
+    unsigned int base = 0;
+    if (lane == first) base = atomicAdd(A.next_count, (unsigned int)__popcll(am));
+    base = (unsigned int)__builtin_amdgcn_readlane((int)base, first);
+    const unsigned int at = base + (unsigned int)__popcll(am & ((1ull << lane) - 1ull));
+    if (again && at < (unsigned int)A.npix) A.next[at] = (int)p;
+  }
+}
+
 // [BVH | CSG << 1 | VM << 2], as k_trace_kernels
 const void* const k_camera_kernels[8] = {
     (const void*)rt_trace_kernel<false, false, false, true>, (const void*)rt_trace_kernel<true, false, false, true>,
     (const void*)rt_trace_kernel<false, true, false, true>,  (const void*)rt_trace_kernel<true, true, false, true>,
     (const void*)rt_trace_kernel<false, false, true, true>,  (const void*)rt_trace_kernel<true, false, true, true>,
     (const void*)rt_trace_kernel<false, true, true, true>,   (const void*)rt_trace_kernel<true, true, true, true>};
+
+// ... with the adaptive refill: the passes of rt_render_camera_adaptive_async
+const void* const k_adaptive_kernels[8] = {
+    (const void*)rt_trace_kernel<false, false, false, true, true>, (const void*)rt_trace_kernel<true, false, false, true, true>,
+    (const void*)rt_trace_kernel<false, true, false, true, true>,  (const void*)rt_trace_kernel<true, true, false, true, true>,
+    (const void*)rt_trace_kernel<false, false, true, true, true>,  (const void*)rt_trace_kernel<true, false, true, true, true>,
+    (const void*)rt_trace_kernel<false, true, true, true, true>,   (const void*)rt_trace_kernel<true, true, true, true, true>};
 
 struct CamPlan {
   CamArgs A;
@@ -289,6 +430,45 @@ int cam_setup(rt_context* c, const rt_camera* cam, int y0, int y1, const char* w
   return RT_OK;
 }
 
+// Adaptive renders: the pass schedule and the chunking that goes with it.
+constexpr int CAM_ADAPT_MAX_PASSES = 12;     // min_samples 2 -> cap 1024: 10 passes
+constexpr int CAM_ADAPT_MAX_CHUNK = 524288;  // pixels of a chunk, at most: bounds the state and the lists (28 MiB)
+constexpr size_t CAM_ADAPT_CTL = 256;        // bytes: counts[passes] then tickets[passes], 32-bit each
+
+struct AdaptPlan {
+  double tol2;
+  int passes;
+  int n[CAM_ADAPT_MAX_PASSES];  // samples of an active pixel after pass k
+  int B;                        // the largest batch
+};
+
+// Validate `ad` against the camera of `P` and rework P's chunks for the
+// schedule's largest batch, in the order include/rt_abi.h states.
+int adapt_setup(const rt_adaptive* ad, const rt_camera* cam, const char* who, CamPlan& P, AdaptPlan& D) {
+  const std::string w = std::string(who) + ": ";
+  const int S = P.A.S;
+  if (!ad) return fail(RT_E_INVALID, w + "NULL rt_adaptive");
+  if (ad->reserved != 0) return fail(RT_E_INVALID, w + "rt_adaptive.reserved must be 0");
+  if (S < 2) return fail(RT_E_INVALID, w + "an adaptive render needs a cap of at least 2 samples");
+  const int n0 = ad->min_samples == 0 ? std::min(4, S) : ad->min_samples;
+  if (n0 < 2 || n0 > S) return fail(RT_E_INVALID, w + "min_samples must satisfy 2 <= min_samples <= samples");
+  if (!(ad->tolerance >= 0.0)) return fail(RT_E_INVALID, w + "tolerance must be >= 0 and not NaN");
+  D.tol2 = ad->tolerance * ad->tolerance;
+  D.passes = 0;
+  D.B = n0;
+  for (int n = n0;; n = std::min(2 * n, S)) {
+    if (D.passes > 0) D.B = std::max(D.B, n - D.n[D.passes - 1]);
+    D.n[D.passes++] = n;
+    if (n == S) break;
+  }
+  P.chunk = std::max(1, std::min(CAM_ADAPT_MAX_CHUNK, CAM_BUF_RECORDS / D.B));
+  if (cam && cam->chunk_pixels > 0) P.chunk = std::min(P.chunk, cam->chunk_pixels);
+  const long long nch = (P.pixels + P.chunk - 1) / P.chunk;
+  if (nch > 2147483647LL) return fail(RT_E_INVALID, w + "chunk_pixels cuts the band into more than 2^31 - 1 chunks");
+  P.chunks = (int)nch;
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -357,6 +537,117 @@ int rt_render_camera_async(rt_context* c, const rt_camera* cam, int y0, int y1, 
     void* rargs[] = {(void*)&rec, (void*)&npix, (void*)&S, (void*)&inv, (void*)&px0, (void*)&rgba, (void*)&d_mean};
     HIP_TRY(hipLaunchKernel((const void*)cam_resolve_kernel, dim3((unsigned)((npix + WG - 1) / WG)), dim3(WG), rargs, 0,
                             st));
+  }
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+int rt_render_camera_adaptive_plan(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1,
+                                   int* chunks, int* passes) {
+  const char* who = "rt_render_camera_adaptive_plan";
+  CamPlan P;
+  AdaptPlan D;
+  if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
+  if (int rc = adapt_setup(ad, cam, who, P, D); rc != RT_OK) return rc;
+  if (chunks) *chunks = P.chunks;
+  if (passes) *passes = D.passes;
+  return RT_OK;
+}
+
+int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1,
+                                    void* d_rgba, double* d_mean, int32_t* d_samples, void* stream) {
+  const char* who = "rt_render_camera_adaptive_async";
+  CamPlan P;
+  AdaptPlan D;
+  if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
+  if (int rc = adapt_setup(ad, cam, who, P, D); rc != RT_OK) return rc;
+  if (!d_rgba && !d_mean && !d_samples)
+    return fail(RT_E_INVALID, std::string(who) + ": d_rgba, d_mean and d_samples are all NULL");
+  if (((uintptr_t)d_rgba & 3) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_rgba must be 4-byte aligned");
+  if (((uintptr_t)d_mean & 7) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_mean must be 8-byte aligned");
+  if (((uintptr_t)d_samples & 3) != 0)
+    return fail(RT_E_INVALID, std::string(who) + ": d_samples must be 4-byte aligned");
+  const DevScene& s = c->sc;
+  DeviceGuard guard(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  // the sample buffer (shared with the fixed renders), then the state: both grown when a call needs more
+  const size_t cpix = (size_t)std::min<long long>(P.pixels, P.chunk);  // pixels of the largest chunk
+  const size_t need = cpix * D.B * sizeof(rt_radiance);
+  if (need > c->cam_buf_bytes) {
+    if (c->cam_buf) {
+      HIP_TRY(hipDeviceSynchronize());  // an earlier camera render may still use the old one
+      (void)hipFree(c->cam_buf);
+      c->cam_buf = nullptr;
+      c->cam_buf_bytes = 0;
+    }
+    HIP_TRY(hipMalloc((void**)&c->cam_buf, need));
+    c->cam_buf_bytes = need;
+  }
+  // [counts and tickets][state: 6 doubles per pixel][two lists]
+  const size_t aneed = CAM_ADAPT_CTL + cpix * (6 * sizeof(double) + 2 * sizeof(int));
+  if (aneed > c->cam_adapt_bytes) {
+    if (c->cam_adapt) {
+      HIP_TRY(hipDeviceSynchronize());
+      (void)hipFree(c->cam_adapt);
+      c->cam_adapt = nullptr;
+      c->cam_adapt_bytes = 0;
+    }
+    HIP_TRY(hipMalloc((void**)&c->cam_adapt, aneed));
+    c->cam_adapt_bytes = aneed;
+  }
+  unsigned int* counts = reinterpret_cast<unsigned int*>(c->cam_adapt);
+  unsigned int* tickets = counts + CAM_ADAPT_MAX_PASSES;
+  double* state = reinterpret_cast<double*>(c->cam_adapt + CAM_ADAPT_CTL);
+  int* lists[2] = {reinterpret_cast<int*>(state + 6 * cpix), reinterpret_cast<int*>(state + 6 * cpix) + cpix};
+  // the frame stack for the largest launch of the call, and the argument record every launch starts from
+  TraceArgsT<true> Q0;
+  std::memset(&Q0, 0, sizeof Q0);
+  int wgs_max = 0;
+  if (int rc = trace_prepare(c, (int)cpix * D.B, P.depth, nullptr, c->cam_buf, st, Q0, wgs_max); rc != RT_OK) return rc;
+  Q0.cam = P.A;
+  const int grid = trace_grid_wgs(c, P.depth);
+  const void* kfn = k_adaptive_kernels[(s.use_bvh ? 1 : 0) | (s.has_csg ? 2 : 0) | (s.num_programs > 0 ? 4 : 0)];
+  const char* blob = s.blob;
+  for (long long px0 = 0; px0 < P.pixels; px0 += P.chunk) {
+    const int npix = (int)std::min<long long>(P.chunk, P.pixels - px0);
+    HIP_TRY(hipMemsetAsync(c->cam_adapt, 0, CAM_ADAPT_CTL, st));
+    for (int k = 0; k < D.passes; k++) {
+      const int s0 = k == 0 ? 0 : D.n[k - 1], b = D.n[k] - s0;
+      // pass k reads list k & 1 and counts[k] (pass 0: every pixel), and fills list (k + 1) & 1 and counts[k + 1]
+      const int* list = k == 0 ? nullptr : lists[k & 1];
+      const unsigned int* count = k == 0 ? nullptr : counts + k;
+      TraceArgsT<true> Q = Q0;
+      Q.n = npix * b;
+      Q.ticket = tickets + k;
+      Q.cam.first = P.A.first + (int)px0;
+      Q.cam.s0 = s0;
+      Q.cam.b = b;
+      Q.cam.list = list;
+      Q.cam.count = count;
+      const int wgs = std::min(grid, (Q.n + WG - 1) / WG);
+      void* targs[] = {(void*)&blob, (void*)&Q};
+      HIP_TRY(hipLaunchKernel(kfn, dim3((unsigned)wgs), dim3(WG), targs, 0, st));
+      AdaptArgs R;
+      std::memset(&R, 0, sizeof R);
+      R.rec = c->cam_buf;
+      R.npix = npix;
+      R.b = b;
+      R.n = D.n[k];
+      R.S = P.A.S;
+      R.tol2 = D.tol2;
+      R.list = list;
+      R.count = count;
+      R.next = lists[(k + 1) & 1];
+      R.next_count = counts + k + 1;
+      R.state = state;
+      R.px0 = px0;
+      R.rgba = (uint32_t*)d_rgba;
+      R.mean = d_mean;
+      R.samples = d_samples;
+      void* rargs[] = {(void*)&R};
+      HIP_TRY(hipLaunchKernel((const void*)cam_adapt_kernel, dim3((unsigned)((npix + WG - 1) / WG)), dim3(WG), rargs, 0,
+                              st));
+    }
   }
   HIP_TRY(hipGetLastError());
   return RT_OK;

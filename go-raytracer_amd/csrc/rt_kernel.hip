@@ -612,6 +612,8 @@ struct rt_context {
   unsigned int* trace_ticket = nullptr;
   rt_radiance* cam_buf = nullptr;  // camera renders' sample records of one chunk (rt_camera.hip)
   size_t cam_buf_bytes = 0;
+  char* cam_adapt = nullptr;  // adaptive camera renders: counts and tickets, pixel state, two lists (rt_camera.hip)
+  size_t cam_adapt_bytes = 0;
 };
 
 namespace {
@@ -1595,6 +1597,7 @@ void rt_destroy(rt_context* c) {
   (void)hipFree(c->trace_ws);
   (void)hipFree(c->trace_ticket);
   (void)hipFree(c->cam_buf);
+  (void)hipFree(c->cam_adapt);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   delete c;

@@ -76,7 +76,10 @@ struct __attribute__((aligned(16))) R16 {
 // VM: the scene has closure surfaces (run_vm's register file lives in scratch)
 // GEN: ticket t is sample t % S of the launch's pixel t / S and the lane forms
 // that ray itself (cam_ticket_ray, rt_camera.hip) instead of loading Q.rays[t]
-template <bool BVH, bool CSG, bool VM, bool GEN>
+// ADP (with GEN; adaptive camera renders only): the pass's tickets go through
+// its pixel list and batch, and their number is read from device memory
+// (cam_ticket_limit), clamped to Q.n
+template <bool BVH, bool CSG, bool VM, bool GEN, bool ADP = false>
 __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict__ blob, TraceArgsT<GEN> Q) {
   __shared__ uint64_t s_mask[BVH ? WAVES_PER_WG * BVH_STACK : 1];
   __shared__ int s_ref[BVH ? WAVES_PER_WG * BVH_STACK : 1];
@@ -272,6 +275,8 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
   double tmax = __builtin_inf();
   int excl = -1;
   bool drained = false;  // every ray index has been handed out (wave-uniform)
+  unsigned int lim = (unsigned int)Q.n;  // tickets of the launch
+  if constexpr (GEN && ADP) lim = cam_ticket_limit(Q.cam, lim);
 
   for (;;) {
     // idle lanes take the next ray indices
@@ -283,11 +288,11 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
         unsigned int base = 0;
         if (lane == first) base = atomicAdd(Q.ticket, cnt);
         base = (unsigned int)__builtin_amdgcn_readlane((int)base, first);
-        if (base + cnt >= (unsigned int)Q.n) drained = true;
+        if (base + cnt >= lim) drained = true;
         const unsigned int mine = base + (unsigned int)__popcll(im & ((1ull << lane) - 1ull));
-        if (!act && base < (unsigned int)Q.n && mine < (unsigned int)Q.n) {
+        if (!act && base < lim && mine < lim) {
           if constexpr (GEN) {
-            cam_ticket_ray(Q.cam, mine, ray.o, ray.d);
+            cam_ticket_ray(Q.cam, mine, BoolC<ADP>(), ray.o, ray.d);
             tmax = __builtin_inf();
             excl = -1;
           } else {

@@ -107,6 +107,10 @@ def load_library(path=None):
     l.rt_render_camera_async.restype = i
     l.rt_render_camera_chunks.argtypes = [vp, vp, i, i]
     l.rt_render_camera_chunks.restype = i
+    l.rt_render_camera_adaptive_async.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp]
+    l.rt_render_camera_adaptive_async.restype = i
+    l.rt_render_camera_adaptive_plan.argtypes = [vp, vp, vp, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    l.rt_render_camera_adaptive_plan.restype = i
     if l.rt_abi_version() != abi.RT_ABI_VERSION:
         raise RenderError("librtamd ABI version mismatch")
     _lib = l
@@ -533,6 +537,70 @@ class RenderContext:
         if n < 0:
             _check(n, "rt_render_camera_chunks")
         return n
+
+    # ---- adaptive camera renders (include/rt_abi.h rt_adaptive, rt_render_camera_adaptive_async) ----
+    @staticmethod
+    def adaptive(tolerance, min_samples=0):
+        """An abi.rt_adaptive: pixels stop once the standard error of their
+        mean is at most `tolerance` in every channel, after at least
+        `min_samples` samples (0: min(4, the camera's samples))."""
+        ad = abi.rt_adaptive()
+        ad.tolerance = float(tolerance)
+        ad.min_samples = int(min_samples)
+        return ad
+
+    def render_camera_adaptive_async(self, cam, ad, y0, y1, rgba=None, mean=None, samples=None, stream=None):
+        """Enqueue the adaptive camera render of rows [y0, y1) of `cam`'s
+        frame, whose samples are the cap, into any of `rgba` (uint8 [rows, W,
+        4]), `mean` (float64 [rows, W, 3]) and `samples` (int32 [rows, W]: the
+        samples each pixel took), all CUDA tensors. Ordering as
+        render_camera_async."""
+        torch = self.torch
+        who = "render_camera_adaptive_async"
+        cam, w, _, _ = self._camera_frame(cam)
+        rows = max(0, int(y1) - int(y0))
+        rp = mp = sp = None
+        if rgba is not None:
+            assert rgba.dtype == torch.uint8, who + ": rgba must be a uint8 tensor"
+            rp = self._camera_out(rgba, rows * w * 4, who, "rgba")
+        if mean is not None:
+            assert mean.dtype == torch.float64, who + ": mean must be a float64 tensor"
+            mp = self._camera_out(mean, rows * w * 24, who, "mean")
+        if samples is not None:
+            assert samples.dtype == torch.int32, who + ": samples must be an int32 tensor"
+            sp = self._camera_out(samples, rows * w * 4, who, "samples")
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_render_camera_adaptive_async(self.handle, C.byref(cam), C.byref(ad), int(y0), int(y1), rp, mp,
+                                                        sp, C.c_void_p(s.cuda_stream)),
+               "rt_render_camera_adaptive_async")
+
+    def render_camera_adaptive(self, cam, ad, y0=0, y1=None, mean=False, samples=False):
+        """Synchronous adaptive camera render of rows [y0, y1) -> numpy uint8
+        [rows, W, 4]; with mean=True and / or samples=True -> a tuple of that,
+        the float64 [rows, W, 3] mean radiance and the int32 [rows, W] sample
+        counts, in this order."""
+        torch = self.torch
+        cam, w, h, _ = self._camera_frame(cam)
+        if y1 is None:
+            y1 = h
+        rows = max(0, y1 - y0)
+        dev = "cuda:%d" % self.device
+        rgba = torch.empty((rows, w, 4), dtype=torch.uint8, device=dev)
+        m = torch.empty((rows, w, 3), dtype=torch.float64, device=dev) if mean else None
+        n = torch.empty((rows, w), dtype=torch.int32, device=dev) if samples else None
+        self.render_camera_adaptive_async(cam, ad, y0, y1, rgba, m, n)
+        torch.cuda.synchronize(self.device)
+        out = [t.cpu().numpy() for t in (rgba, m, n) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def render_camera_adaptive_plan(self, cam, ad, y0=0, y1=None):
+        """(chunks, passes per chunk) render_camera_adaptive_async launches for these arguments."""
+        cam, _, h, _ = self._camera_frame(cam)
+        chunks, passes = C.c_int(0), C.c_int(0)
+        _check(self.lib.rt_render_camera_adaptive_plan(self.handle, C.byref(cam), C.byref(ad), int(y0),
+                                                       int(h if y1 is None else y1), C.byref(chunks), C.byref(passes)),
+               "rt_render_camera_adaptive_plan")
+        return chunks.value, passes.value
 
     def image_from_radiance(self, out, samples):
         """Average `samples` consecutive radiance records per pixel and quantise

@@ -671,6 +671,68 @@ int rt_render_camera_async(rt_context *ctx, const rt_camera *cam, int y0, int y1
  * arguments; negative: the RT_E_INVALID it would return (buffers aside). */
 int rt_render_camera_chunks(rt_context *ctx, const rt_camera *cam, int y0, int y1);
 
+/* Adaptive camera renders: per-pixel sample counts chosen on the device.
+ * Everything is FP64, one rounding per operation, no contraction, in the order
+ * written here.
+ * Cap and draws: S = cam->samples (0: 4) is the cap and also the draw stride:
+ * sample s of pixel (x, y) is exactly sample s of rt_render_camera_async with
+ * the same camera -- same draws, same ray. A pixel that ends with n = S
+ * samples is that render's pixel, bit for bit.
+ * Schedule: n_0 = min_samples (0: min(4, S)), n_(k+1) = min(2 * n_k, S) until
+ * n_K = S. Pass 0 traces samples [0, n_0) of every pixel, pass k samples
+ * [n_(k-1), n_k) of every pixel still active: all active pixels of a pass hold
+ * the same n.
+ * State of a pixel: Sum_c and Q_c start as c_0 and c_0 * c_0; then for
+ * s = 1, 2, ... in sample order Sum_c = Sum_c + c_s and
+ * Q_c = Q_c + (c_s * c_s), per channel c. Sum is the fixed render's ordered sum.
+ * Stopping rule after a pass that leaves n samples:
+ *   inv = 1.0 / (double)n;  m_c = Sum_c * inv;  v_c = Q_c - Sum_c * m_c;
+ *   e_c = v_c / (double)(n * (n - 1))   (the squared standard error of the mean)
+ * the pixel is converged iff e_c <= tol2 for all three channels, with
+ * tol2 = tolerance * tolerance formed once on the host (false for NaN; a
+ * negative v_c passes).
+ * A pixel becomes final when it is converged or n = S: its mean is m_c, its
+ * bytes uint8(uint32(m_c * 65535) >> 8) with alpha 255 as above, its sample
+ * count n. Other pixels stay active for the next pass. */
+typedef struct rt_adaptive {
+    int32_t min_samples;        /* 0: min(4, samples); else 2 <= min_samples <= samples */
+    int32_t reserved;           /* must be 0 */
+    double  tolerance;          /* >= 0, not NaN; +inf: every pixel stops at min_samples */
+} rt_adaptive;
+
+/* Render rows [y0, y1) of the camera's frame adaptively into any of d_rgba and
+ * d_mean (laid out as for rt_render_camera_async) and d_samples (one int32 per
+ * pixel, [row][x], 4-byte aligned: the pixel's sample count); not all three
+ * NULL. Device pointers only. RT_E_INVALID (with an rt_last_error text) for
+ * everything rt_render_camera_async rejects, and: NULL ad, reserved != 0, a
+ * cap below 2 samples, min_samples outside [2, samples], a negative or NaN
+ * tolerance, all outputs NULL, a misaligned output. Nothing is launched then
+ * and the context stays usable.
+ * Chunks: max(1, min(524288, 2097152 / B)) consecutive pixels, B the largest
+ * batch n_k - n_(k-1) of the schedule (chunk_pixels if that is smaller). Per
+ * chunk the call enqueues on `stream`: one reset of the chunk's pass counts
+ * and tickets, then per pass one launch of the radiance kernel -- ticket t is
+ * sample n_(k-1) + t % b of the pass's active pixel t / b, b = n_k - n_(k-1),
+ * and the launch reads its number of active pixels from device memory -- and
+ * one launch that continues the pixels' sums, applies the rule, writes the
+ * final pixels and lists the others for the next pass. The host never waits
+ * and never learns how many pixels are active. The order of a list may differ
+ * from run to run; no output depends on it.
+ * Memory, context-owned, grown when a call needs more (which waits for the
+ * device), freed by rt_destroy: the camera renders' sample buffer (at most
+ * 64 MiB) and at most 28 MiB of pixel state and lists.
+ * Side effects and ordering: as rt_render_camera_async (none on renders,
+ * counters, specialisation and tile order; to be ordered with the other
+ * camera renders and the radiance queries of the context). */
+int rt_render_camera_adaptive_async(rt_context *ctx, const rt_camera *cam, const rt_adaptive *ad, int y0, int y1,
+                                    void *d_rgba, double *d_mean, int32_t *d_samples, void *stream);
+
+/* The launches rt_render_camera_adaptive_async makes for these arguments:
+ * *chunks chunks of *passes passes each (either may be NULL). RT_OK, or the
+ * RT_E_INVALID the render would return (buffers aside). */
+int rt_render_camera_adaptive_plan(rt_context *ctx, const rt_camera *cam, const rt_adaptive *ad, int y0, int y1,
+                                   int *chunks, int *passes);
+
 /* SSIM of two RGBA8 frames in device memory (width x height, stride 4W), the
  * reference's parity metric prim.SSIM (internal/prim/ssim.go:27-182; used by
  * raytracer_test.go:42 with threshold 0.99). Synchronous on `stream`.

@@ -27,7 +27,20 @@ events around 5 frames after 1 warm-up, with the times of each chunk's trace +
 resolve, and beside rt_render_rows_async generic and specialised. On c3 also
 S = 1, 4, 16, 64. Every line asserts that the fused bytes equal render()'s.
 
-usage: python scripts/query_rate.py [--configs c3,c4csg,c5] [--modes closest,occluded,radiance,camera] [--out FILE]
+Adaptive mode (not in the default modes; writes
+profiles/adaptive/adaptive_rate.jsonl unless --out says otherwise): the zero
+camera at 1920x1080 with a cap of 64 samples through
+rt_render_camera_adaptive_async, min_samples 4, tolerances 0.002 and 0.005,
+beside the fixed 64-sample rt_render_camera_async of the same build -- three
+runs each of device events around 5 frames after 1 warm-up. Per line: both
+times, the mean samples per pixel and the histogram of the counts, passes x
+chunks launched, and rt_ssim_rgba8 and the largest byte difference against the
+fixed 64-sample frame; also the time of the same call at an infinite
+tolerance (every pass after the first is empty: what the launches alone cost)
+and of the fixed render at min_samples.
+
+usage: python scripts/query_rate.py [--configs c3,c4csg,c5] [--modes closest,occluded,radiance,camera,adaptive]
+                                    [--out FILE]
 """
 import argparse
 import json
@@ -149,6 +162,52 @@ def camera_line(torch, abi, ctx, name, seed):
     return line
 
 
+ADAPT_CAP, ADAPT_MIN, ADAPT_TOLS = 64, 4, (0.002, 0.005)
+
+
+def adaptive_lines(torch, abi, ctx, name, seed):
+    """The adaptive render of the zero camera at a cap of 64 samples beside
+    the fixed 64-sample render: one line per tolerance."""
+    cam = ctx.camera(samples=ADAPT_CAP)
+    fixed = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0")
+    rgba = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0")
+    cnt = torch.empty((H, W), dtype=torch.int32, device="cuda:0")
+    fixed_ms = [timed(torch, lambda: ctx.render_camera_async(cam, 0, H, rgba=fixed), RAD_WARMUP, RAD_LAUNCHES)
+                for _ in range(3)]
+    # what the launches alone cost: an infinite tolerance stops every pixel at min_samples, so passes 1.. are
+    # empty, beside the fixed render at min_samples (one trace launch per chunk, the same rays)
+    stop = ctx.adaptive(math.inf, ADAPT_MIN)
+    empty_ms = timed(torch, lambda: ctx.render_camera_adaptive_async(cam, stop, 0, H, rgba=rgba, samples=cnt),
+                     RAD_WARMUP, RAD_LAUNCHES)
+    low = ctx.camera(samples=ADAPT_MIN)
+    low_ms = timed(torch, lambda: ctx.render_camera_async(low, 0, H, rgba=rgba), RAD_WARMUP, RAD_LAUNCHES)
+    lines = []
+    for tol in ADAPT_TOLS:
+        ad = ctx.adaptive(tol, ADAPT_MIN)
+        ms = [timed(torch, lambda: ctx.render_camera_adaptive_async(cam, ad, 0, H, rgba=rgba, samples=cnt), RAD_WARMUP,
+                    RAD_LAUNCHES) for _ in range(3)]
+        torch.cuda.synchronize()
+        chunks, passes = ctx.render_camera_adaptive_plan(cam, ad)
+        v, k = torch.unique(cnt, return_counts=True)
+        hist = {int(a): int(b) for a, b in zip(v.tolist(), k.tolist())}
+        mean_spp = float(cnt.sum(dtype=torch.int64).item()) / (W * H)
+        diff = int((rgba.to(torch.int16) - fixed.to(torch.int16)).abs().max().item())
+        am, fm = min(ms), min(fixed_ms)
+        lines.append({"metric": "adaptive_rate", "config": name, "mode": "adaptive", "width": W, "height": H,
+                      "cap": ADAPT_CAP, "min_samples": ADAPT_MIN, "tolerance": tol,
+                      "depth": int(ctx.packed.scene.depth), "objects": int(ctx.packed.scene.num_objects),
+                      "bvh": bool(ctx.scene_info() & abi.RT_INFO_BVH),
+                      "adaptive_ms": [round(x, 4) for x in ms], "fixed_ms": [round(x, 4) for x in fixed_ms],
+                      "fixed_chunks": ctx.render_camera_chunks(cam), "passes": passes, "chunks": chunks,
+                      "trace_launches": passes * chunks, "mean_samples": round(mean_spp, 4), "histogram": hist,
+                      "time_ratio": round(am / fm, 4), "ray_ratio": round(mean_spp / ADAPT_CAP, 4),
+                      "ssim_vs_fixed": ctx.ssim(rgba, fixed), "max_byte_diff": diff,
+                      "empty_passes_ms": round(empty_ms, 4), "fixed_min_samples_ms": round(low_ms, 4),
+                      "fixed_min_samples_chunks": ctx.render_camera_chunks(low),
+                      "launches": RAD_LAUNCHES, "warmup": RAD_WARMUP, "runs": 3, "seed": seed})
+    return lines
+
+
 def camera_rays(fov_deg, seed):
     g = np.random.default_rng(seed)
     vw = 2.0 * math.tan(math.radians(fov_deg) / 2.0)
@@ -207,7 +266,16 @@ def main():
         if "camera" in modes:
             lines.append(camera_line(torch, abi, ctx, name, args.seed))
             print(json.dumps(lines[-1]), flush=True)
+        if "adaptive" in modes:
+            for ln in adaptive_lines(torch, abi, ctx, name, args.seed):
+                lines.append(ln)
+                print(json.dumps(ln), flush=True)
     ctx.close()
+    if args.out is None and "adaptive" in args.modes.split(","):
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "adaptive",
+                                "adaptive_rate.jsonl")
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        lines = [ln for ln in lines if ln["mode"] == "adaptive"]
     if args.out is None and "camera" in args.modes.split(","):
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "camera",
                                 "camera_rate.jsonl")
