@@ -45,6 +45,13 @@
 // k = 0..16, are compile-time constants, and the lane applies the maps of the
 // set bits of its offset (pcg_jump, as the render kernel does with its
 // host-built table).
+//
+// Shared pieces used here, each defined once elsewhere: ray_store and flavour
+// (rt_query.hip); wave_take, the wave-aggregated atomicAdd of the adaptive list
+// append, and ray_out_check (rt_trace.hip: wave_take has to precede the
+// radiance kernel, whose ticket refill is its other caller); grow and
+// need_scene (rt_kernel.hip, beside the context). pack_rgba8 below serves both
+// the resolve and the adapt kernel.
 // Included by rt_kernel.hip after rt_trace.hip.
 
 namespace {
@@ -184,13 +191,15 @@ __global__ __launch_bounds__(WG) void cam_rays_kernel(CamArgs A, long long n, rt
   const long long p = tid / A.S;
   d3 o, d;
   cam_ray(A, A.first + (int)p, (int)(tid - p * A.S), o, d);
-  Q16* rp = reinterpret_cast<Q16*>(out + tid);
-  const Q16 r0 = {o.x, o.y}, r1 = {o.z, d.x}, r2 = {d.y, d.z};
-  rp[0] = r0;
-  rp[1] = r1;
-  rp[2] = r2;
-  const R16 r3 = {__builtin_inf(), -1, 0};
-  *reinterpret_cast<R16*>(rp + 3) = r3;
+  ray_store(out + tid, o, d);
+}
+
+// A pixel's mean colour quantised as Render() does: 16 bits, the high byte kept
+__device__ __forceinline__ uint32_t pack_rgba8(const d3& c) {
+  const uint32_t r8 = go_f64_to_u32(c.x * 65535.0) >> 8;
+  const uint32_t g8 = go_f64_to_u32(c.y * 65535.0) >> 8;
+  const uint32_t b8 = go_f64_to_u32(c.z * 65535.0) >> 8;
+  return (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
 }
 
 // One thread per pixel of a chunk: the pixel's S records (two 16-byte loads
@@ -215,12 +224,7 @@ __global__ __launch_bounds__(WG) void cam_resolve_kernel(const rt_radiance* __re
     mean[q * 3 + 1] = c.y;
     mean[q * 3 + 2] = c.z;
   }
-  if (rgba) {
-    const uint32_t r8 = go_f64_to_u32(c.x * 65535.0) >> 8;
-    const uint32_t g8 = go_f64_to_u32(c.y * 65535.0) >> 8;
-    const uint32_t b8 = go_f64_to_u32(c.z * 65535.0) >> 8;
-    rgba[q] = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
-  }
+  if (rgba) rgba[q] = pack_rgba8(c);
 }
 
 // One pass of an adaptive render (include/rt_abi.h "Adaptive camera renders").
@@ -292,12 +296,7 @@ __global__ __launch_bounds__(WG) void cam_adapt_kernel(AdaptArgs A) {
         A.mean[q * 3 + 1] = m.y;
         A.mean[q * 3 + 2] = m.z;
       }
-      if (A.rgba) {
-        const uint32_t r8 = go_f64_to_u32(m.x * 65535.0) >> 8;
-        const uint32_t g8 = go_f64_to_u32(m.y * 65535.0) >> 8;
-        const uint32_t b8 = go_f64_to_u32(m.z * 65535.0) >> 8;
-        A.rgba[q] = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
-      }
+      if (A.rgba) A.rgba[q] = pack_rgba8(m);
       if (A.samples) A.samples[q] = A.n;
     } else {
       st[0] = sum.x;
@@ -311,12 +310,8 @@ __global__ __launch_bounds__(WG) void cam_adapt_kernel(AdaptArgs A) {
   }
   const uint64_t am = wave_ballot(again);
   if (am) {
-    const int lane = (int)(threadIdx.x & 63);
-    const int first = __builtin_amdgcn_readfirstlane(__builtin_ctzll(am));
-    unsigned int base = 0;
-    if (lane == first) base = atomicAdd(A.next_count, (unsigned int)__popcll(am));
-    base = (unsigned int)__builtin_amdgcn_readlane((int)base, first);
-    const unsigned int at = base + (unsigned int)__popcll(am & ((1ull << lane) - 1ull));
+    unsigned int base;
+    const unsigned int at = wave_take(A.next_count, am, (int)(threadIdx.x & 63), base);
     if (again && at < (unsigned int)A.npix) A.next[at] = (int)p;
   }
 }
@@ -349,8 +344,7 @@ bool cam_finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(
 // and derive the launch's camera, in the order include/rt_abi.h states.
 int cam_setup(rt_context* c, const rt_camera* cam, int y0, int y1, const char* who, CamPlan& P) {
   const std::string w = std::string(who) + ": ";
-  if (!c) return fail(RT_E_INVALID, w + "NULL context");
-  if (!c->has_scene) return fail(RT_E_INVALID, w + "no scene set");
+  if (int rc = need_scene(c, who); rc != RT_OK) return rc;
   rt_camera z;
   std::memset(&z, 0, sizeof z);
   if (cam) z = *cam;
@@ -430,6 +424,13 @@ int cam_setup(rt_context* c, const rt_camera* cam, int y0, int y1, const char* w
   return RT_OK;
 }
 
+// The pixel outputs both renders share
+int cam_out_check(const void* d_rgba, const double* d_mean, const char* who) {
+  if (((uintptr_t)d_rgba & 3) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_rgba must be 4-byte aligned");
+  if (((uintptr_t)d_mean & 7) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_mean must be 8-byte aligned");
+  return RT_OK;
+}
+
 // Adaptive renders: the pass schedule and the chunking that goes with it.
 constexpr int CAM_ADAPT_MAX_PASSES = 12;     // min_samples 2 -> cap 1024: 10 passes
 constexpr int CAM_ADAPT_MAX_CHUNK = 524288;  // pixels of a chunk, at most: bounds the state and the lists (28 MiB)
@@ -477,8 +478,7 @@ int rt_camera_rays_async(rt_context* c, const rt_camera* cam, int y0, int y1, rt
   const char* who = "rt_camera_rays_async";
   CamPlan P;
   if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
-  if (!d_rays) return fail(RT_E_INVALID, std::string(who) + ": NULL ray pointer");
-  if (((uintptr_t)d_rays & 15) != 0) return fail(RT_E_INVALID, std::string(who) + ": ray array must be 16-byte aligned");
+  if (int rc = ray_out_check(d_rays, who); rc != RT_OK) return rc;
   DeviceGuard guard(c->device);
   long long n = P.pixels * P.A.S;
   const long long blocks = (n + WG - 1) / WG;
@@ -501,25 +501,15 @@ int rt_render_camera_async(rt_context* c, const rt_camera* cam, int y0, int y1, 
   CamPlan P;
   if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
   if (!d_rgba && !d_mean) return fail(RT_E_INVALID, std::string(who) + ": d_rgba and d_mean are both NULL");
-  if (((uintptr_t)d_rgba & 3) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_rgba must be 4-byte aligned");
-  if (((uintptr_t)d_mean & 7) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_mean must be 8-byte aligned");
+  if (int rc = cam_out_check(d_rgba, d_mean, who); rc != RT_OK) return rc;
   const DevScene& s = c->sc;
   DeviceGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
   int S = P.A.S;
   // the sample buffer: grown when a call needs more (calls on a context are ordered)
   const size_t need = (size_t)std::min<long long>(P.pixels, P.chunk) * S * sizeof(rt_radiance);
-  if (need > c->cam_buf_bytes) {
-    if (c->cam_buf) {
-      HIP_TRY(hipDeviceSynchronize());  // an earlier camera render may still use the old one
-      (void)hipFree(c->cam_buf);
-      c->cam_buf = nullptr;
-      c->cam_buf_bytes = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&c->cam_buf, need));
-    c->cam_buf_bytes = need;
-  }
-  const void* kfn = k_camera_kernels[(s.use_bvh ? 1 : 0) | (s.has_csg ? 2 : 0) | (s.num_programs > 0 ? 4 : 0)];
+  if (int rc = grow(c->cam_buf, c->cam_buf_bytes, need); rc != RT_OK) return rc;
+  const void* kfn = k_camera_kernels[flavour(s)];
   const char* blob = s.blob;
   const rt_radiance* rec = c->cam_buf;
   uint32_t* rgba = (uint32_t*)d_rgba;
@@ -563,8 +553,7 @@ int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const r
   if (int rc = adapt_setup(ad, cam, who, P, D); rc != RT_OK) return rc;
   if (!d_rgba && !d_mean && !d_samples)
     return fail(RT_E_INVALID, std::string(who) + ": d_rgba, d_mean and d_samples are all NULL");
-  if (((uintptr_t)d_rgba & 3) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_rgba must be 4-byte aligned");
-  if (((uintptr_t)d_mean & 7) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_mean must be 8-byte aligned");
+  if (int rc = cam_out_check(d_rgba, d_mean, who); rc != RT_OK) return rc;
   if (((uintptr_t)d_samples & 3) != 0)
     return fail(RT_E_INVALID, std::string(who) + ": d_samples must be 4-byte aligned");
   const DevScene& s = c->sc;
@@ -573,28 +562,10 @@ int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const r
   // the sample buffer (shared with the fixed renders), then the state: both grown when a call needs more
   const size_t cpix = (size_t)std::min<long long>(P.pixels, P.chunk);  // pixels of the largest chunk
   const size_t need = cpix * D.B * sizeof(rt_radiance);
-  if (need > c->cam_buf_bytes) {
-    if (c->cam_buf) {
-      HIP_TRY(hipDeviceSynchronize());  // an earlier camera render may still use the old one
-      (void)hipFree(c->cam_buf);
-      c->cam_buf = nullptr;
-      c->cam_buf_bytes = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&c->cam_buf, need));
-    c->cam_buf_bytes = need;
-  }
+  if (int rc = grow(c->cam_buf, c->cam_buf_bytes, need); rc != RT_OK) return rc;
   // [counts and tickets][state: 6 doubles per pixel][two lists]
   const size_t aneed = CAM_ADAPT_CTL + cpix * (6 * sizeof(double) + 2 * sizeof(int));
-  if (aneed > c->cam_adapt_bytes) {
-    if (c->cam_adapt) {
-      HIP_TRY(hipDeviceSynchronize());
-      (void)hipFree(c->cam_adapt);
-      c->cam_adapt = nullptr;
-      c->cam_adapt_bytes = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&c->cam_adapt, aneed));
-    c->cam_adapt_bytes = aneed;
-  }
+  if (int rc = grow(c->cam_adapt, c->cam_adapt_bytes, aneed); rc != RT_OK) return rc;
   unsigned int* counts = reinterpret_cast<unsigned int*>(c->cam_adapt);
   unsigned int* tickets = counts + CAM_ADAPT_MAX_PASSES;
   double* state = reinterpret_cast<double*>(c->cam_adapt + CAM_ADAPT_CTL);
@@ -606,7 +577,7 @@ int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const r
   if (int rc = trace_prepare(c, (int)cpix * D.B, P.depth, nullptr, c->cam_buf, st, Q0, wgs_max); rc != RT_OK) return rc;
   Q0.cam = P.A;
   const int grid = trace_grid_wgs(c, P.depth);
-  const void* kfn = k_adaptive_kernels[(s.use_bvh ? 1 : 0) | (s.has_csg ? 2 : 0) | (s.num_programs > 0 ? 4 : 0)];
+  const void* kfn = k_adaptive_kernels[flavour(s)];
   const char* blob = s.blob;
   for (long long px0 = 0; px0 < P.pixels; px0 += P.chunk) {
     const int npix = (int)std::min<long long>(P.chunk, P.pixels - px0);

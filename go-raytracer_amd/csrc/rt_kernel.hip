@@ -629,6 +629,30 @@ struct DeviceGuard {
   }
 };
 
+// The first checks of an entry point that works on the context's scene
+int need_scene(const rt_context* c, const char* who) {
+  if (!c) return fail(RT_E_INVALID, std::string(who) + ": NULL context");
+  if (!c->has_scene) return fail(RT_E_INVALID, std::string(who) + ": no scene set");
+  return RT_OK;
+}
+
+// Grow a context-owned device buffer to `need` bytes (calls on a context are
+// ordered). Work enqueued earlier may still use the old buffer: the device is
+// synchronised before it is freed. A failed allocation leaves p null, have 0.
+template <typename T>
+int grow(T*& p, size_t& have, size_t need) {
+  if (need <= have) return RT_OK;
+  if (p) {
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(p);
+    p = nullptr;
+    have = 0;
+  }
+  HIP_TRY(hipMalloc((void**)&p, need));
+  have = need;
+  return RT_OK;
+}
+
 void free_scene(DevScene& s) {
   (void)hipFree(s.blob);
   (void)hipFree(s.accel);

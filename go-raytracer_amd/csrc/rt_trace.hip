@@ -7,9 +7,10 @@
 // closestHit, ComputeSurfaceProps (closure surfaces through run_vm),
 // computeLighting with inShadow per light, the reflection and refraction
 // children and the final combine -- with the exact tests of rt_render.h called
-// unchanged (object_hit, csg_hit, run_vm, go_pow, combine) and the SHADE block
-// of rt_render_kernel repeated op for op, so a query returns the colour a
-// render sums for that ray, bit for bit.
+// unchanged (object_hit, csg_hit, run_vm, go_pow, combine), the search shared
+// with the query kernel (SceneSearch, rt_query.hip) and the SHADE block of
+// rt_render_kernel repeated op for op, so a query returns the colour a render
+// sums for that ray, bit for bit.
 //
 // Persistent, bounded grid: trace_grid_wgs() workgroups whatever n is. Each
 // lane holds one ray tree at a time; a lane that finishes takes the next ray
@@ -25,9 +26,9 @@
 // grid (trace_grid_wgs).
 //
 // Per iteration, wave-lock-step: refill idle lanes, closest search for the
-// lanes that hold a ray (the wave-uniform object loop / BVH walk of
-// rt_query.hip), shade the lanes that hit (one any-hit search per light), then
-// push a frame and descend or pop frames and combine.
+// lanes that hold a ray (SceneSearch of rt_query.hip, closest mode), shade the
+// lanes that hit (the same search in any-hit mode once per light), then push a
+// frame and descend or pop frames and combine.
 //
 // Ray directions are used as given; the FP32 culls get a unit direction and
 // bounds scaled by |dir|, and composites of a wave that holds a non-unit
@@ -41,6 +42,11 @@ enum { TR_LW = 0, TR_KR = 3, TR_PK = 4, TR_EXT = 5, TR_COL = 11, TR_REFL = 14, T
 enum { TR_WG_PER_CU = 2 };                        // full grid: 2 workgroups (8 waves) per CU
 constexpr size_t TR_WS_MAX = (size_t)128 << 20;  // bytes of frame stack per context, at most
 
+// SceneRef's fields (rt_query.hip; filled by scene_ref, read by SceneSearch) are
+// written out among the kernel's own, in this order, and not inherited: with
+// SceneRef as a base, or placed after the other fields, most instantiations
+// spill more SGPRs (up to 18) and c4csg radiance queries ran 2.3 % slower
+// (DESIGN.md "Shared pieces ...", BASELINE.md "Shared search: same speed").
 struct TraceArgs {
   const rt_ray* rays;
   rt_radiance* out;
@@ -57,21 +63,22 @@ struct TraceArgs {
   double bvh_lo[3], bvh_hi[3];
 };
 
-template <bool B>
-struct BoolC {
-  static constexpr bool value = B;
-};
-
 // The kernel's argument record. GEN (camera renders, rt_camera.hip): the
 // specialisation for true, defined there, adds the camera the lanes form their
 // rays from; without GEN this is TraceArgs itself.
 template <bool GEN>
 struct TraceArgsT : TraceArgs {};
 
-struct __attribute__((aligned(16))) R16 {
-  double z;
-  int object, rays;
-};
+// The lanes of ballot `m` (not 0) take consecutive values of *ctr with one
+// atomic per wave: the first lane of m adds their number, `base` is what it
+// read, and a lane of m gets base + its rank in m (returned).
+__device__ __forceinline__ unsigned int wave_take(unsigned int* ctr, uint64_t m, int lane, unsigned int& base) {
+  const int first = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
+  base = 0;
+  if (lane == first) base = atomicAdd(ctr, (unsigned int)__popcll(m));
+  base = (unsigned int)__builtin_amdgcn_readlane((int)base, first);
+  return base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+}
 
 // VM: the scene has closure surfaces (run_vm's register file lives in scratch)
 // GEN: ticket t is sample t % S of the launch's pixel t / S and the lane forms
@@ -89,179 +96,12 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
   auto fld = [&](int level, int f) -> double& { return stk[((size_t)level * TR_FIELDS + f) * nl]; };
 
   // scene records through scalar loads (wave-uniform indices)
-  const cdptr cs_geo = (cdptr)(blob + Q.off_geo);
-  const cdptr cs_shade = (cdptr)(blob + Q.off_shade);
-  const ciptr cs_kind = (ciptr)(blob + Q.off_kind);
-  const ciptr cs_csg = (ciptr)(blob + Q.off_csg);
-  (void)cs_csg;
   const cdptr G = (cdptr)(blob + Q.off_lights);  // GLOB record, then the lights
   const cdptr lights = G + GLOB;
   // ... through vector loads (per-lane indices)
-  const double* v_geo = reinterpret_cast<const double*>(blob + Q.off_geo);
-  const double* v_shade = reinterpret_cast<const double*>(blob + Q.off_shade);
   const double* v_mats = reinterpret_cast<const double*>(blob + Q.off_mats);
-  const int* v_kind = reinterpret_cast<const int*>(blob + Q.off_kind);
-  const int* v_objmat = reinterpret_cast<const int*>(blob + Q.off_objmat);
-  const bool cull = Q.cull != 0;
-
-  // One search over the scene for the lanes in `act`. Closest mode (OC false):
-  // closestHit with `tmax` and `excl` as in rt_query_closest_async. Any-hit
-  // mode (OC true): inShadow's loop for the hit on object `excl`, an occluder
-  // being a result with t * rl < dist (raytracer.go:424); `found` then says
-  // occluded, whichever occluder was met first (the verdict is the same).
-  auto search = [&](const Ray& ray, bool act, double tmax, int excl, auto oc, double rl, double dist, bool& found,
-                    double& best_t, int& best_i, int& best_f) {
-    constexpr bool occl = decltype(oc)::value;
-    // the culls' ray: unit direction, bounds in world units (see the head of rt_query.hip)
-    const F3 of = f3(ray.o);
-    const float slack = ray_slack(of);
-    double dlen = 1.0;
-    F3 df;
-    bool cullok;
-    if constexpr (occl) {
-      df = f3(ray.d);
-      cullok = slack < 1e30f;
-    } else {
-      dlen = __builtin_sqrt(dot(ray.d, ray.d));
-      const float dlf = (float)dlen;
-      cullok = dlf > 1e-18f && dlf < 1e18f && slack < 1e30f;
-      df = f3(scale(ray.d, 1.0 / dlen));
-    }
-    const bool nocull = !cullok;  // this lane passes every cull
-    bool unit_dir = true;
-    if constexpr (CSG) unit_dir = wave_all(!act || __builtin_fabs(dot(ray.d, ray.d) - 1.0) <= 1e-9);
-    bool open = act;  // still searching (any-hit mode: not yet occluded)
-    found = false;
-    best_t = 0.0;
-    best_i = 0;
-    best_f = 0;
-    const double slim = occl ? dist / rl : 0.0;
-    // the bound a candidate has to stay below
-    auto limit = [&]() { return occl ? slim : (found ? best_t : tmax); };
-    auto bound_f = [&](double t0) {
-      const double lim = limit();
-      return lim < __builtin_inf() ? (float)((lim - t0) * dlen) * 1.0001f + 1e-4f : 3.0e38f;
-    };
-    auto exact = [&](int i, int k, const double* g, bool test) {
-      if (test) {
-        double t;
-        int f;
-        bool h;
-        if constexpr (CSG) {
-          if (k == RT_CSG) {
-            const auto cg = cs_geo + (size_t)i * GEO;
-            if constexpr (occl)
-              h = unit_dir ? csg_hit<true>(cs_geo, cs_kind, cs_csg, Q.nobj, cg, ray, t, f, rl, dist, false)
-                           : csg_search_nocull<true>(cs_geo, cs_kind, cs_csg, Q.nobj, cg, ray, t, f, __builtin_inf(),
-                                                     false);
-            else
-              h = unit_dir ? csg_hit<true>(cs_geo, cs_kind, cs_csg, Q.nobj, cg, ray, t, f, 1.0, limit(), true)
-                           : csg_search_nocull<true>(cs_geo, cs_kind, cs_csg, Q.nobj, cg, ray, t, f, limit(), true);
-          } else {
-            h = object_hit(k, g, ray, t, f);
-          }
-        } else {
-          h = object_hit(k, g, ray, t, f);
-        }
-        if constexpr (occl) {
-          if (h && t * rl < dist) {
-            found = true;
-            open = false;
-          }
-        } else {
-          if (h && t < tmax && (!found || t < best_t || (BVH && t == best_t && i < best_i))) {
-            found = true;
-            best_t = t;
-            best_i = i;
-            best_f = f;
-          }
-        }
-      }
-    };
-    // object i of an index-order list: the culls (when on), then the exact test
-    auto list_obj = [&](int i) {
-      const int k = cs_kind[i];
-      double gl[GEO];
-#pragma unroll
-      for (int q = 0; q < GEO; q++) gl[q] = cs_geo[(size_t)i * GEO + q];
-      bool test = open && i != excl;
-      if (cull) {
-        const float tm = bound_f(0.0);
-        const bool c = k != RT_PLANE ? may_hit_a(test, of, df, tm, gl, slack)
-                                     : CULL_AND(test, may_hit_plane(of, df, tm, cs_shade + (size_t)i * SHD));
-        test = c || (test && nocull);
-      }
-      if (!wave_any(test)) return;
-      exact(i, k, gl, test);
-    };
-
-    if constexpr (!BVH) {
-      for (int i = 0; i < Q.nobj; i++) {
-        if (occl && !wave_any(open)) break;
-        list_obj(i);
-      }
-    } else {
-      WaveStack bst;
-      bst.mask = s_mask + (threadIdx.x >> 6) * BVH_STACK;
-      bst.ref = s_ref + (threadIdx.x >> 6) * BVH_STACK;
-      for (int p = 0; p < Q.nplanes; p++) {  // unbounded objects: planes, composites
-        if (occl && !wave_any(open)) break;
-        list_obj(__builtin_amdgcn_readfirstlane(Q.planes[p]));
-      }
-      const F3 idf = f3_rcp(df);
-      // far origins: the BVH culls' origin, slack and bounds (see far_shift)
-      F3 bof = of;
-      float bslack = slack;
-      double bt0 = 0.0;
-      bool btr = open;
-      bool fsh = btr && cullok;  // (a lane that passes every cull keeps its origin)
-      far_shift(fsh, ray, Q.bvh_lo, Q.bvh_hi, bof, bslack, bt0);
-      if (cullok) btr = fsh;
-      int ssp = 0;
-      int nr = 0;  // the node visited next, kept in registers (see RT_BVH_CONT)
-      uint64_t nm = wave_ballot(btr);
-      bool have = nm != 0;
-      for (;;) {
-        int r;
-        uint64_t m;
-        if (have) {
-          r = nr;
-          m = nm;
-          have = false;
-        } else {
-          if (ssp == 0) break;
-          ssp--;
-          r = __builtin_amdgcn_readfirstlane(bst.ref[ssp]);
-          m = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(bst.mask[ssp] >> 32)) << 32) |
-              (uint32_t)__builtin_amdgcn_readfirstlane((int)bst.mask[ssp]);
-        }
-        // (any-hit mode: a lane leaves the walk once it is occluded)
-        const bool wact = btr && open && ((m >> lane) & 1);
-        if (occl && !wave_any(open)) break;
-        if (r & 7) {  // leaf
-          const int first = r >> 3, count = r & 7;
-          for (int j = first; j < first + count; j++) {
-            const LeafRec L = ld_leaf(Q.bvh_geo, j);  // scalar loads (wave-uniform index)
-            const bool la = wact && open && L.i != excl;
-            const bool test = may_hit_s(la, bof, df, bound_f(bt0), L.cx, L.cy, L.cz, L.cr, bslack) || (la && nocull);
-            if (!wave_any(test)) continue;
-            exact(L.i, L.k, L.R.m, test);
-          }
-        } else {
-          const cfptr nb = (cfptr)Q.bvh_nodes + (size_t)(r >> 3) * BN;  // scalar loads
-          const ciptr ni = (ciptr)(nb + 12);
-          const float tm = bound_f(bt0);
-          float t0 = 0.0f, t1 = 0.0f;  // (set by may_hit_box_a when it returns true)
-          const bool a0 = may_hit_box_a(wact, bof, idf, bslack, tm, nb, t0) || (wact && nocull);
-          const bool a1 = may_hit_box_a(wact, bof, idf, bslack, tm, nb + 6, t1) || (wact && nocull);
-          const uint64_t m0 = wave_ballot(a0), m1 = wave_ballot(a1);
-          // near child first: the one most lanes enter first
-          const bool c1_first = 2 * __popcll(wave_ballot(a0 && a1 && t1 < t0)) > __popcll(m0 & m1);
-          bvh_next(bst, ssp, lane, c1_first, ni[0], ni[1], m0, m1, nr, nm, have);
-        }
-      }
-    }
-  };
+  // closestHit and inShadow's loop (rt_query.hip)
+  auto search = scene_search<BVH, CSG>(blob, Q, s_mask, s_ref);
 
   // the lane's ray tree
   bool act = false;  // holds a ray to trace
@@ -283,26 +123,16 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
     if (!drained) {
       const uint64_t im = wave_ballot(!act);
       if (im) {
-        const int first = __builtin_amdgcn_readfirstlane(__builtin_ctzll(im));
-        const unsigned int cnt = (unsigned int)__popcll(im);
-        unsigned int base = 0;
-        if (lane == first) base = atomicAdd(Q.ticket, cnt);
-        base = (unsigned int)__builtin_amdgcn_readlane((int)base, first);
-        if (base + cnt >= lim) drained = true;
-        const unsigned int mine = base + (unsigned int)__popcll(im & ((1ull << lane) - 1ull));
+        unsigned int base;
+        const unsigned int mine = wave_take(Q.ticket, im, lane, base);
+        if (base + (unsigned int)__popcll(im) >= lim) drained = true;
         if (!act && base < lim && mine < lim) {
           if constexpr (GEN) {
             cam_ticket_ray(Q.cam, mine, BoolC<ADP>(), ray.o, ray.d);
             tmax = __builtin_inf();
             excl = -1;
           } else {
-            // the lane's ray: four 16-byte loads of its 64-byte record
-            const Q16* rp = reinterpret_cast<const Q16*>(Q.rays + mine);
-            const Q16 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
-            ray.o = mk(r0.a, r0.b, r1.a);
-            ray.d = mk(r1.b, r2.a, r2.b);
-            tmax = r3.a;
-            excl = __double2loint(r3.b);
+            ray_load(Q.rays + mine, ray, tmax, excl);
           }
           idx = (int)mine;
           sp = 0;
@@ -318,7 +148,7 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
     bool found;
     double hit_t;
     int hit_i, hit_f;
-    search(ray, act, tmax, excl, BoolC<false>(), 1.0, 0.0, found, hit_t, hit_i, hit_f);
+    search(ray, act, tmax, excl, BoolC<false>(), BoolC<false>(), 1.0, 0.0, found, hit_t, hit_i, hit_f);
     if (act && sp == 0) top = found ? hit_i : -1;
     bool have_res = false;
     d3 res = mk(0, 0, 0);
@@ -335,6 +165,14 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
       double vr[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // a closure surface's material (rt_material order)
       (void)vr;
       if (hit) {
+        // surface_props (rt_query.hip) written out: called as a function, in
+        // any form tried, it costs <1, 0, 0> 40 VGPRs and a wave per SIMD
+        // (DESIGN.md "Shared pieces of the query, radiance and camera
+        // kernels"). Keep the two in step.
+        const double* v_geo = reinterpret_cast<const double*>(blob + Q.off_geo);
+        const double* v_shade = reinterpret_cast<const double*>(blob + Q.off_shade);
+        const int* v_kind = reinterpret_cast<const int*>(blob + Q.off_kind);
+        const int* v_objmat = reinterpret_cast<const int*>(blob + Q.off_objmat);
         int si = hit_i, sf = hit_f;  // the surface: the object, or a CSG composite's leaf
         bool flip = false;
         if constexpr (CSG) {
@@ -432,7 +270,8 @@ __global__ __launch_bounds__(WG, 2) void rt_trace_kernel(const char* __restrict_
         bool shadowed;
         double st;
         int si_, sf_;
-        search(sr, hit, __builtin_inf(), hit_i, BoolC<true>(), rlen, dist, shadowed, st, si_, sf_);
+        // (unit length: ldir is normalised above)
+        search(sr, hit, __builtin_inf(), hit_i, BoolC<true>(), BoolC<true>(), rlen, dist, shadowed, st, si_, sf_);
         if (hit && !shadowed) {
           d3 lcol = mk(lt[3], lt[4], lt[5]);
           if (lkind == RT_LIGHT_SPOT) {  // extension: cone falloff
@@ -624,13 +463,7 @@ __global__ __launch_bounds__(WG) void rt_camera_rays_kernel(const char* __restri
       const double v = ((double)y + dy) / H1 * vh - vh / 2.0;
       const d3 o = mk(u, -v, 0.0);
       const d3 d = norm(sub(o, eye));
-      Q16* rp = reinterpret_cast<Q16*>(out + ((size_t)(y - y0) * width + x) * 4 + k);
-      const Q16 r0 = {o.x, o.y}, r1 = {o.z, d.x}, r2 = {d.y, d.z};
-      rp[0] = r0;
-      rp[1] = r1;
-      rp[2] = r2;
-      const R16 r3 = {__builtin_inf(), -1, 0};
-      *reinterpret_cast<R16*>(rp + 3) = r3;
+      ray_store(out + ((size_t)(y - y0) * width + x) * 4 + k, o, d);
     }
   }
 }
@@ -659,6 +492,13 @@ int trace_depth(const rt_context* c, const char* who, int depth, int* out) {
   return RT_OK;
 }
 
+// The output pointer of a camera-ray export
+int ray_out_check(const rt_ray* d_rays, const char* who) {
+  if (!d_rays) return fail(RT_E_INVALID, std::string(who) + ": NULL ray pointer");
+  if (((uintptr_t)d_rays & 15) != 0) return fail(RT_E_INVALID, std::string(who) + ": ray array must be 16-byte aligned");
+  return RT_OK;
+}
+
 // What a launch of n tickets at depth D needs before it: the grid, the frame
 // stack (grown when a call needs more: calls on a context are ordered), the
 // zeroed ticket and the argument record (zero-filled by the caller).
@@ -667,47 +507,22 @@ int trace_prepare(rt_context* c, int n, int D, const rt_ray* d_rays, rt_radiance
   const DevScene& s = c->sc;
   const int wgs = std::min(trace_grid_wgs(c, D), (n + WG - 1) / WG);
   const size_t need = (size_t)std::max(1, D - 1) * TR_FIELDS * sizeof(double) * WG * (size_t)wgs;
-  if (need > c->trace_ws_bytes) {
-    if (c->trace_ws) {
-      HIP_TRY(hipDeviceSynchronize());  // an earlier query may still use the old one
-      (void)hipFree(c->trace_ws);
-      c->trace_ws = nullptr;
-      c->trace_ws_bytes = 0;
-    }
-    HIP_TRY(hipMalloc((void**)&c->trace_ws, need));
-    c->trace_ws_bytes = need;
-  }
+  if (int rc = grow(c->trace_ws, c->trace_ws_bytes, need); rc != RT_OK) return rc;
   if (!c->trace_ticket) HIP_TRY(hipMalloc((void**)&c->trace_ticket, 64));
   HIP_TRY(hipMemsetAsync(c->trace_ticket, 0, sizeof(unsigned int), stream));
+  scene_ref(c, Q);
   Q.rays = d_rays;
   Q.out = d_out;
   Q.ticket = c->trace_ticket;
   Q.ws = c->trace_ws;
   Q.n = n;
-  Q.nobj = s.nobj;
   Q.depth = D;
   Q.nlights = s.nlights;
-  Q.cull = (c->accel & RT_ACCEL_CULL) ? 1 : 0;
-  Q.off_geo = s.off_geo;
-  Q.off_shade = s.off_shade;
-  Q.off_kind = s.off_kind;
-  Q.off_objmat = s.off_objmat;
-  Q.off_csg = s.off_csg;
   Q.off_mats = s.off_mats;
   Q.off_lights = s.off_lights;
   Q.off_code = s.off_code;
   Q.off_consts = s.off_consts;
   Q.off_entry = s.off_entry;
-  if (s.use_bvh) {
-    Q.bvh_nodes = reinterpret_cast<const float*>(s.accel + s.off_nodes);
-    Q.bvh_geo = reinterpret_cast<const double*>(s.accel + s.off_bobj);
-    Q.planes = reinterpret_cast<const int*>(s.accel + s.off_planes);
-    Q.nplanes = s.nplanes;
-    for (int k = 0; k < 3; k++) {
-      Q.bvh_lo[k] = s.bvh_lo[k];
-      Q.bvh_hi[k] = s.bvh_hi[k];
-    }
-  }
   wgs_out = wgs;
   return RT_OK;
 }
@@ -718,8 +533,7 @@ extern "C" {
 
 int rt_query_radiance_async(rt_context* c, int n, const rt_ray* d_rays, int depth, rt_radiance* d_out, void* stream) {
   const char* who = "rt_query_radiance_async";
-  if (!c) return fail(RT_E_INVALID, std::string(who) + ": NULL context");
-  if (!c->has_scene) return fail(RT_E_INVALID, std::string(who) + ": no scene set");
+  if (int rc = need_scene(c, who); rc != RT_OK) return rc;
   if (n < 0) return fail(RT_E_INVALID, std::string(who) + ": n < 0");
   int D = 0;
   if (int rc = trace_depth(c, who, depth, &D); rc != RT_OK) return rc;
@@ -735,7 +549,7 @@ int rt_query_radiance_async(rt_context* c, int n, const rt_ray* d_rays, int dept
   if (int rc = trace_prepare(c, n, D, d_rays, d_out, (hipStream_t)stream, Q, wgs); rc != RT_OK) return rc;
   const char* blob = s.blob;
   void* args[] = {(void*)&blob, (void*)&Q};
-  const void* kfn = k_trace_kernels[(s.use_bvh ? 1 : 0) | (s.has_csg ? 2 : 0) | (s.num_programs > 0 ? 4 : 0)];
+  const void* kfn = k_trace_kernels[flavour(s)];
   HIP_TRY(hipLaunchKernel(kfn, dim3((unsigned)wgs), dim3(WG), args, 0, (hipStream_t)stream));
   HIP_TRY(hipGetLastError());
   return RT_OK;
@@ -752,13 +566,11 @@ int rt_query_radiance_lanes(rt_context* c, int depth) {
 
 int rt_query_camera_rays_async(rt_context* c, int y0, int y1, rt_ray* d_rays, void* stream) {
   const char* who = "rt_query_camera_rays_async";
-  if (!c) return fail(RT_E_INVALID, std::string(who) + ": NULL context");
-  if (!c->has_scene) return fail(RT_E_INVALID, std::string(who) + ": no scene set");
+  if (int rc = need_scene(c, who); rc != RT_OK) return rc;
   const DevScene& s = c->sc;
   if (y0 < 0 || y1 > s.height || y0 >= y1)
     return fail(RT_E_INVALID, std::string(who) + ": rows must satisfy 0 <= y0 < y1 <= height");
-  if (!d_rays) return fail(RT_E_INVALID, std::string(who) + ": NULL ray pointer");
-  if (((uintptr_t)d_rays & 15) != 0) return fail(RT_E_INVALID, std::string(who) + ": ray array must be 16-byte aligned");
+  if (int rc = ray_out_check(d_rays, who); rc != RT_OK) return rc;
   DeviceGuard guard(c->device);
   const int nstrips = (y1 - 1) / 20 - y0 / 20 + 1;
   const long long threads = (long long)s.width * nstrips;

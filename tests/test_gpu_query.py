@@ -331,3 +331,27 @@ def test_unit_directions_equal_the_oracle(ctx, name):
     ctx.set_scene(Q.packed(name))
     assert_hits_equal(gpu_closest(ctx, o, d), want, name + " unit directions")
     assert np.array_equal(gpu_occluded(ctx, o, d, tmax=4.0).astype(bool), occ)
+
+
+# 11. the any-hit bound is strict exactly at the closest hit: with tmax = t of
+# the oracle's winner nothing occludes, one ulp further the winner does. Unit
+# directions take the composite search with its leaf culls and its cut at the
+# bound, longer ones the search without either (the head of rt_query.hip).
+@pytest.mark.parametrize("length", [1.0, 3.0])
+@pytest.mark.parametrize("name", ["mixed11", "mixed12", "c4csg"])
+def test_occluded_bound_is_strict_at_the_closest_hit(ctx, name, length):
+    T0 = Q.table(name)
+    o, d = T0.origins[:256], T0.dirs[:256]
+    d = d / np.linalg.norm(d, axis=1)[:, None] * length
+    T = Q.Table(Q.packed(name), o, d)
+    first = T.closest()
+    hit = first["object"] >= 0
+    assert hit.sum() >= 50
+    at = np.where(hit, first["t"], np.inf)
+    past = np.where(hit, np.nextafter(first["t"], np.inf), np.inf)
+    want_at, want_past = T.occluded(tmax=at), T.occluded(tmax=past)
+    assert not want_at.any() and np.array_equal(want_past, hit)
+    ctx.set_scene(Q.packed(name))
+    assert bool(ctx.scene_info() & abi.RT_INFO_BVH) == (name == "mixed12")
+    assert np.array_equal(gpu_occluded(ctx, o, d, tmax=at).astype(bool), want_at)
+    assert np.array_equal(gpu_occluded(ctx, o, d, tmax=past).astype(bool), want_past)
