@@ -31,12 +31,7 @@ __device__ __forceinline__ d3 scale(d3 a, double s) { return mk(a.x * s, a.y * s
 //   result = class(x', +-0 | +inf) ? x' : g
 // For 2^-767 <= x < inf the scaling steps are the identity and the class
 // test is false, so the core below gives the same bits in 10 instead of 18
-// VALU instructions.
-#ifndef RT_FAST_SQRT
-// 2: per-lane fix-up form (default; -2.6 % VALU, C3 -0.2..-1.2 %). 1:
-// wave-uniform form (more scalar branch work, no faster). 0: full sequence.
-#define RT_FAST_SQRT 2
-#endif
+// VALU instructions (-2.6 % VALU, C3 -0.2..-1.2 %).
 __device__ __forceinline__ double sqrt_core(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = y * 0.5;
@@ -54,16 +49,12 @@ __device__ __forceinline__ bool wave_all(bool c) {
   return __builtin_amdgcn_ballot_w64(c) == __builtin_amdgcn_read_exec();
 }
 __device__ __forceinline__ double gsqrt(double x) {
-#if RT_FAST_SQRT == 2
-  // every lane takes the core; lanes outside the range redo the full sequence
+  // every lane takes the core; lanes outside the range (2^-767 <= x < inf <=>
+  // high word in [0x10000000, 0x7ff00000), sign clear: one compare) redo the
+  // full sequence
   double g = sqrt_core(x);
   if (__builtin_expect((uint32_t)__double2hiint(x) - 0x10000000u >= 0x6ff00000u, 0)) g = __builtin_sqrt(x);
   return g;
-#elif RT_FAST_SQRT
-  // 2^-767 <= x < inf  <=>  high word in [0x10000000, 0x7ff00000) (sign clear; one compare)
-  if (wave_all((uint32_t)__double2hiint(x) - 0x10000000u < 0x6ff00000u)) return sqrt_core(x);
-#endif
-  return __builtin_sqrt(x);
 }
 __device__ __forceinline__ double len(d3 v) { return gsqrt(v.x * v.x + v.y * v.y + v.z * v.z); }  // vec.go:95
 // Shared-denominator division, bit-identical to `/`. hipcc lowers an FP64
@@ -90,15 +81,6 @@ __device__ __forceinline__ double div_rcp(double n, double d, double y) {
   const double q = n * y;
   return __builtin_copysign(__builtin_fma(__builtin_fma(-d, q, n), y, q), n);
 }
-__device__ __forceinline__ uint64_t num_ok(double n) {
-  return __builtin_amdgcn_ballot_w64(__builtin_fabs(n) >= 0x1p-800) | __builtin_amdgcn_ballot_w64(n == 0.0);
-}
-#ifndef RT_FAST_NORM
-// 2: per-lane fix-up form (default; C3 -2.3 % wave cycles). 1: wave-uniform
-// form (more scalar branch work). 0: hardware divisions.
-#define RT_FAST_NORM 2
-#endif
-#if RT_FAST_NORM == 2
 // The branch-free half of norm_len: core sqrt and shared-reciprocal quotients,
 // ok = false where a lane must redo them with the hardware sequences
 // (norm_len_fix), so that several normalisations can share one fix-up branch.
@@ -115,10 +97,8 @@ __device__ __forceinline__ d3 norm_len_fix(d3 v, double& m) {
   m = __builtin_sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
   return mk(v.x / m, v.y / m, v.z / m);
 }
-#endif
 // norm(v) that also hands back |v| (the same bits as len(v)).
 __device__ __forceinline__ d3 norm_len(d3 v, double& m) {                                        // vec.go:78,95
-#if RT_FAST_NORM == 2
   // Every lane takes the core square root and the shared-reciprocal
   // quotients; lanes outside their ranges redo both with the full hardware
   // sequences under one (rarely entered) branch. x = m^2 in [2^-200, 2^198)
@@ -126,25 +106,11 @@ __device__ __forceinline__ d3 norm_len(d3 v, double& m) {                       
   // correctly rounded and monotone; 2^198 keeps a round-up to 2^100 out).
   // Numerators: +-0 or |n| >= 2^-800 <=> frexp exponent >= -799 (a zero's
   // exponent is 0, a denormal's < -1021; inf/NaN components fail on x).
+  // (C3 -2.3 % wave cycles against hardware divisions.)
   bool ok;
   d3 r = norm_len_core(v, m, ok);
   if (__builtin_expect(!ok, 0)) r = norm_len_fix(v, m);
   return r;
-#else
-  m = gsqrt(v.x * v.x + v.y * v.y + v.z * v.z);
-#endif
-#if RT_FAST_NORM == 1
-  // d in [2^-100, 2^100): high word in [0x39B00000, 0x46300000) (one compare)
-  const uint64_t ok = __builtin_amdgcn_ballot_w64((uint32_t)__double2hiint(m) - 0x39B00000u < 0x0C800000u) &
-                      num_ok(v.x) & num_ok(v.y) & num_ok(v.z);
-  if (ok == __builtin_amdgcn_read_exec()) {
-    const double y = rcp_refined(m);
-    return mk(div_rcp(v.x, m, y), div_rcp(v.y, m, y), div_rcp(v.z, m, y));
-  }
-#endif
-#if RT_FAST_NORM != 2
-  return mk(v.x / m, v.y / m, v.z / m);
-#endif
 }
 __device__ __forceinline__ d3 norm(d3 v) {  // vec.go:78
   double m;
@@ -426,11 +392,8 @@ __device__ __noinline__ double go_pow_general(double x, double y, int mode) {
 // Ldexp loop below (same ops, same order); x == 0 takes its zero case. The
 // general routine (with the exp/log fraction path) stays out of line: inlined
 // it doubled the kernel's register spills.
-#ifndef RT_POW_DIRECT
-#define RT_POW_DIRECT 1  // exact direct binary powering for small integer exponents (see go_pow)
-#endif
 __device__ __forceinline__ double go_pow(double x, double y, int mode = 2) {
-#if RT_POW_DIRECT
+  // Exact direct binary powering for small integer exponents.
   // Integer 2 <= y <= 64 and 2^-15 <= x <= 2^15: every power the loop below
   // forms (x^(2^k) for 2^k <= y, and the partial products, all between x^y and
   // 1) is a normal number, where round-to-nearest commutes with scaling by
@@ -449,7 +412,6 @@ __device__ __forceinline__ double go_pow(double x, double y, int mode = 2) {
     }
     return a1;
   }
-#endif
   if (x > 0 && x < __builtin_inf() && x != 1 && y >= 2 && y < 2147483648.0 && __builtin_floor(y) == y) {
     int xe;
     double x1 = frexp(x, &xe);

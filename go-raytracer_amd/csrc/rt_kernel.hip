@@ -63,7 +63,7 @@
 #include "rt_device.h"
 
 // The generic kernels run at 3 waves/SIMD like the specialised ones
-// (RT_MIN_WAVES from rt_render.h). Round 3 had dropped them to 2 after a
+// (MIN_WAVES in rt_render.h). Round 3 had dropped them to 2 after a
 // build rendered 14 deep-glass tiles of a reduced C4 frame wrong in the
 // serial-sample schedule; rebuilding that tree at 3 waves with each of its two
 // candidate fixes (profiles/r04/generic/) reproduced the failure exactly
@@ -328,19 +328,9 @@ bool axis_sphere(const double* m) {
   return true;
 }
 
-#ifndef RT_BVH_SAH
-#define RT_BVH_SAH 1  // binned-SAH splits (median split when degenerate)
-#endif
-// Scenes with at least this many bounded objects use the BVH flavour.
-#ifndef RT_FAR_MIN_OBJ
-#define RT_FAR_MIN_OBJ 1024  // BVH scenes from this many objects keep the far-origin shift when specialised
-#endif
-#ifndef RT_BVH_LEAF
-#define RT_BVH_LEAF 4  // objects per BVH leaf (<= 7: the leaf ref holds the count in 3 bits)
-#endif
-#ifndef RT_BVH_MIN
-#define RT_BVH_MIN 12
-#endif
+enum { BVH_MIN = 12,          // scenes with at least this many bounded objects use the BVH flavour
+       BVH_LEAF = 4,          // objects per BVH leaf (<= 7: the leaf ref holds the count in 3 bits)
+       FAR_MIN_OBJ = 1024 };  // BVH scenes from this many objects keep the far-origin shift when specialised
 
 float f_down(double x) {
   float f = (float)x;
@@ -391,7 +381,7 @@ struct BvhBuild {
       out.box[k] = f_down(bl[k]);
       out.box[3 + k] = f_up(bh[k]);
     }
-    if (hi - lo <= RT_BVH_LEAF) {
+    if (hi - lo <= BVH_LEAF) {
       std::sort(ord.begin() + lo, ord.begin() + hi);
       const int first = (int)(leaf_geo.size() / GEO);
       for (int j = lo; j < hi; j++) {
@@ -399,7 +389,7 @@ struct BvhBuild {
         leaf_geo.insert(leaf_geo.end(), geo->begin() + (size_t)i * GEO, geo->begin() + (size_t)(i + 1) * GEO);
         int* gi = reinterpret_cast<int*>(&leaf_geo[leaf_geo.size() - GEO + 14]);
         gi[0] = i;
-        // scale + translation sphere: the kernel may take the diagonal transform (rt_render.h axis_o)
+        // the axis word (a scale + translation sphere): part of the record's layout; the kernels no longer read it
         gi[1] = (*kind)[i] == RT_SPHERE && axis_sphere(&(*geo)[(size_t)i * GEO]) ? 1 : 0;
         gi[2] = (*kind)[i];
         gi[3] = 0;
@@ -411,7 +401,6 @@ struct BvhBuild {
     for (int k = 1; k < 3; k++)
       if (ch[k] - cl[k] > ch[axis] - cl[axis]) axis = k;
     int mid = -1;
-#if RT_BVH_SAH
     // Binned SAH over the centroids (16 bins per axis): minimise
     // area(left) * n(left) + area(right) * n(right); down to the median split
     // when every centroid lands in one bin or below depth 40 (keeps the depth,
@@ -486,7 +475,6 @@ struct BvhBuild {
         if (mid <= lo || mid >= hi) mid = -1;
       }
     }
-#endif
     if (mid < 0) {
       mid = (lo + hi) / 2;
       std::nth_element(ord.begin() + lo, ord.begin() + mid, ord.begin() + hi, [&](int a, int b) {
@@ -529,7 +517,7 @@ struct SpecKey {
   int nocull = 0;                        // rt_set_accel without RT_ACCEL_CULL: -DRT_CULL=0
   int quads = 0;                         // pixel schedule: SCH_SERIAL / SCH_QUADS / SCH_PAIRS (pick_schedule)
   int share = 0;                         // work sharing at the tail (rt_set_work_sharing): -DRT_SHARE=<mode>
-  int far = 1;                           // 0: -DRT_FAR_SHIFT=0 (BVH scenes below RT_FAR_MIN_OBJ objects)
+  int far = 1;                           // 0: -DRT_FAR_SHIFT=0 (BVH scenes below FAR_MIN_OBJ objects)
   std::string str() const {
     return std::to_string(lds) + ":" + std::to_string(bvh) + ":" + std::to_string(csg) + ":" + std::to_string(nobj) + ":" + kinds + ":" +
            std::to_string(kmask) + ":" + std::to_string(feat) + ":" + std::to_string(nlights) + ":" + std::to_string(pow_bits) +
@@ -964,7 +952,7 @@ bool spec_key(const DevScene& s, SpecKey* k) {
   // the BVH culls' far-origin shift (rt_render.h far_shift) pays where a
   // far ray would otherwise sweep many leaves (C5 serial 347 -> 120 ms); a
   // small BVH only carries its registers (C4 +3 %)
-  k->far = (!s.use_bvh || s.nobj >= RT_FAR_MIN_OBJ) ? 1 : 0;
+  k->far = (!s.use_bvh || s.nobj >= FAR_MIN_OBJ) ? 1 : 0;
   return true;
 }
 
@@ -2089,7 +2077,7 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
     std::vector<int> bounded, planes;
     for (int i = 0; i < s.nobj; i++) (kind[i] == RT_PLANE || kind[i] == RT_CSG ? planes : bounded).push_back(i);
     BvhBuild b;
-    if ((c->accel & RT_ACCEL_BVH) && (int)bounded.size() >= RT_BVH_MIN) {
+    if ((c->accel & RT_ACCEL_BVH) && (int)bounded.size() >= BVH_MIN) {
       b.c = &bcen;
       b.r = &brad;
       b.geo = &geo;
@@ -2357,7 +2345,7 @@ static int launch(rt_context* c, int y0, int y1, int trow0, int stride, int ntro
   const int stack_off = vm_off + ((lds && s.num_programs) ? WG * MAT * (int)sizeof(double) : 0);
   const int cnt_off = stack_off + (s.use_bvh ? WAVES_PER_WG * BVH_STACK * 12 : 0);
   const int qmask_off = cnt_off + CNT_BYTES;
-  // per-wave object-record stream buffers (global linear scenes, RT_STREAM)
+  // per-wave object-record stream buffers (global linear scenes, rt_render.h stream_objects)
   const int jump_off = qmask_off + 16;  // after the drained-head mask: the sample-0 jump rows
   const int board_off = jump_off + 20 * 4 * (int)sizeof(uint64_t);  // work-sharing board (RT_SHARE)
   const uint64_t launch_pixels = (uint64_t)s.width * (uint64_t)(stride > 0 ? ntrows * TILE : y1 - y0);

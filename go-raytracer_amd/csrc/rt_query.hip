@@ -319,7 +319,7 @@ struct SceneSearch {
       far_shift(fsh, ray, Q.bvh_lo, Q.bvh_hi, bof, bslack, bt0);
       if (cullok) btr = fsh;
       int ssp = 0;
-      int nr = 0;  // the node visited next, kept in registers (see RT_BVH_CONT)
+      int nr = 0;  // the node visited next, kept in registers (see rt_render.h bvh_next)
       uint64_t nm = wave_ballot(btr);
       bool have = nm != 0;
       for (;;) {

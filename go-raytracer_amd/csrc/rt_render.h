@@ -19,74 +19,65 @@
 #include "rt_abi.h"
 #include "rt_device.h"
 
+// ---------------------------------------------------------------------------
+// Every macro a build may set, with who sets it. Anything else in this file
+// is a constant: change it in place.
+// ---------------------------------------------------------------------------
+// The specialisation key (rt_kernel.hip spec_compile passes these to hipRTC;
+// scripts/spec_regs.sh and spec_matrix.sh pass the same offline):
+//   RT_SPEC_NOBJ, RT_SPEC_KINDS  object count and kinds of a small LDS scene
+//                                (undefined: read from the blob at run time)
+//   RT_SPEC_KMASK, RT_SPEC_FEAT  kinds and features the scene may hold
+//                                (undefined: the generic build, every branch)
+//   RT_SPEC_NLIGHTS              light count (undefined: P.nlights)
+//   RT_SPEC_POWBITS              rt_device.h pow_small_int
+#ifndef RT_CULL
+#define RT_CULL 1  // wave-uniform conservative bounding-sphere culling (exact, see may_hit); 0: brute force
+#endif
+#ifndef RT_SHARE
+#define RT_SHARE 0  // work sharing at the tail: 1 workgroup board, 2 device-wide (see Board, gs_*)
+#endif
+// Pixel pairs (the host's RT_SCHED_PAIRS): with the serial-sample flavour
+// (QUADS = false), a pixel's samples 0-1 run in an even lane and 2-3 in the
+// odd lane after it; the even lane adds the four colours in sample order.
+#ifndef RT_PAIRS
+#define RT_PAIRS 0
+#endif
+#ifndef RT_FAR_SHIFT
+#define RT_FAR_SHIFT 1  // far-origin shift of the BVH culls (see far_shift)
+#endif
+// Set by tests through RT_SPEC_EXTRA_FLAGS (tests/test_gpu_schedule.py):
+#ifndef RT_GS_POLL
+// a busy wave reads the device-wide board's words every (RT_GS_POLL + 1)-th
+// round (c4csg 8-rank share, profiles/r05/gpoll: 1.77-1.79 ms at 3, 1.77-1.81
+// at 1, 1.83 at 0, 1.95 at 15; sharded rings make frequent polls cheap)
+#define RT_GS_POLL 3
+#endif
+#ifndef RT_GS_HELPERS
+#define RT_GS_HELPERS 16  // drained waves that stay to help (device-wide); the others leave at once
+#endif
+// Macros so that a bad value fails the compile (tests/test_gpu_render_api.py
+// forces a compile error through RT_SHADE_NUM):
 #ifndef RT_SHADE_NUM
 #define RT_SHADE_NUM 3  // shade when >= NUM/DEN of the wave's busy lanes hold a hit
 #endif
 #ifndef RT_SHADE_DEN
 #define RT_SHADE_DEN 4
 #endif
-#ifndef RT_DIV_SKIP
-#define RT_DIV_SKIP 0  // skip divisions whose sign proves t <= 0 (exact, see t_nonpos): measured
-                       // slower -- a skip pays only when the whole wave skips, the tests and
-                       // branches are paid always
+// Diagnostic builds, never the product path (csrc/Makefile `phase`, scripts/):
+//   RT_PHASE_TIMING  wave cycles per phase and work-sharing events (PH_*, SHDIAG)
+//   RT_EXACT_DIAG    exact-test counts after culling (EXDIAG)
+//   RT_CSG_DIAG      composite-search counters (g_csg_diag)
+//   RT_COST_MAP      node visits per pixel instead of colours
+#ifdef RT_COST_MAP
+#undef RT_SHARE
+#define RT_SHARE 0  // the cost-map diagnostic charges a pixel's work to its own lane
 #endif
-// Framebuffer stores (raytracer.go:656): a lane holds its finished pixel and
-// the wave stores all held pixels with one instruction when a holder is about
-// to finish another pixel, and at exit -- instead of one store per scheduling
-// round in which some lane finished (0: store at once, A/B).
-#ifndef RT_PIX_BATCH
-#define RT_PIX_BATCH 1
-#endif
-// Pixel pairs (specialised kernels, the host's RT_SCHED_PAIRS): with the
-// serial-sample flavour (QUADS = false), a pixel's samples 0-1 run in an even
-// lane and 2-3 in the odd lane after it; the even lane adds the four colours
-// in sample order.
-#ifndef RT_PAIRS
-#define RT_PAIRS 0
-#endif
-#ifndef RT_FRAME_PREFETCH
-#define RT_FRAME_PREFETCH 1  // load the parent frame during the TRACE pass
-#endif
-#ifndef RT_CULL
-#define RT_CULL 1  // wave-uniform conservative bounding-sphere culling (exact, see may_hit)
-#endif
-#ifndef RT_STMAX_F32
-#define RT_STMAX_F32 1  // shadow-ray cull bound dist/|d| from an FP32 reciprocal (exact: bound only; C3 -1..-1.7 %)
-#endif
-#ifndef RT_STREAM_PREFETCH
-#define RT_STREAM_PREFETCH 0  // next record in registers while the current one is tested: measured slower
-                              // (brute-force C5 480x270: 2.98 vs 2.51 s; 2x / 4x unrolling also slower)
-#endif
-#ifndef RT_STREAM
-#define RT_STREAM 1  // global linear scenes: object records stream through per-wave LDS buffers
-#endif
-#ifndef RT_STREAM_SMEM
-#define RT_STREAM_SMEM 1  // ... or, in the brute-force build (RT_CULL=0), through scalar loads in kind runs
-#endif
-#ifndef RT_SHADOW_JOINT
-#define RT_SHADOW_JOINT 1  // brute force, specialised light count: one sweep for all shadow rays of a hit
-#endif
-#ifndef RT_SHADOW_CHECK
-#define RT_SHADOW_CHECK 8  // brute-force shadow runs: wave-level "any ray open?" test every N objects
-#endif
-#ifndef RT_CULL_NOBRANCH
-#define RT_CULL_NOBRANCH 1  // cull tests combined without short-circuit branches (see CULL_AND)
-#endif
+
 // a && b for the pure, cheap lane predicates of the culls: evaluated on every
 // lane without a branch (no exec-mask save/restore, and the result stays a
 // lane mask for the wave's any-lane test instead of being rematerialised)
-#if RT_CULL_NOBRANCH
 #define CULL_AND(a, b) (bool)((int)(bool)(a) & (int)(bool)(b))
-#else
-#define CULL_AND(a, b) ((a) && (b))
-#endif
-#ifndef RT_AXIS_LEAF
-#define RT_AXIS_LEAF 0  // BVH leaves' scale + translation spheres take the diagonal transform (exact, see axis_o);
-                        // measured: C4 +3 % (a branch per leaf object, more spills), C5 within noise: off
-#endif
-#ifndef RT_CUBE_FAST
-#define RT_CUBE_FAST 1  // axis-aligned cube faces (bit-identical, see cube_hit)
-#endif
 
 using namespace rt;
 
@@ -151,14 +142,11 @@ enum { CHUNK = 64, TILE = 8, WG = 256, WAVES_PER_WG = WG / 64 };
 // Work queue: pixels per dequeue -- one 8x8 tile, or with pixel quads a 4x4
 // quarter of one (16 quads = one wave's lanes) -- from QHEADS queue heads
 // (chunk c belongs to head c mod QHEADS; a workgroup dequeues from head
-// blockIdx mod QHEADS, see RT_QSTEAL), so the dequeue rate
+// blockIdx mod QHEADS, see QSTEAL), so the dequeue rate
 // stays below what one atomic word sustains.
-#ifndef RT_QHEADS
-#define RT_QHEADS 8
-#endif
-enum { QHEADS = RT_QHEADS /* <= 32: the drained-head mask is 32 bits */, QSTRIDE = 16 /* u32 between heads: 64 B */ };
-static_assert(RT_QHEADS >= 1 && RT_QHEADS <= 32, "RT_QHEADS");
-// Heads a workgroup dequeues from: its home head, then RT_QSTEAL others once
+enum { QHEADS = 8 /* <= 32: the drained-head mask is 32 bits */, QSTRIDE = 16 /* u32 between heads: 64 B */ };
+static_assert(QHEADS >= 1 && QHEADS <= 32, "QHEADS");
+// Heads a workgroup dequeues from: its home head, then QSTEAL others once
 // that is drained. Every head is drained by its home workgroups, so stopping
 // early never drops a chunk; it bounds the end-of-launch probes (each a
 // returning atomic, serialised per head address: probing all 8 heads from
@@ -167,15 +155,20 @@ static_assert(RT_QHEADS >= 1 && RT_QHEADS <= 32, "RT_QHEADS");
 // all 7, a one-tile-row launch 85 -> 37 us, C2 0.38 -> 0.33 ms
 // (profiles/r02/qsteal). Not kept: launch-wide drained flags read before
 // stealing (one line written by every overflowing wave: slower).
-#ifndef RT_QSTEAL
-#define RT_QSTEAL 1
-#endif
+enum { QSTEAL = 1 };
 enum { QSET = QHEADS * QSTRIDE /* u32 per launch set of heads */,
-       QSET_ALLOC = 32 * QSTRIDE /* host: room for any RT_QHEADS build */ };
-#ifndef RT_QCHUNK_PIXEL
-#define RT_QCHUNK_PIXEL 64  // pixels per dequeue without quads (a multiple of 16 dividing 64)
-#endif
-enum { SCH = 32 };  // objects per stream chunk (RT_STREAM): SCH * GEO * 8 B + SCH * 4 B per wave
+       QSET_ALLOC = 32 * QSTRIDE /* host: u32 allocated per set (room for 32 heads; QSET of them are used) */ };
+enum { QCHUNK_PIXEL = 64 };  // pixels per dequeue without quads (a multiple of 16 dividing 64)
+// Framebuffer stores (raytracer.go:656): a lane holds its finished pixel and
+// the wave stores all held pixels with one instruction when a holder is about
+// to finish another pixel, and at exit -- instead of one store per scheduling
+// round in which some lane finished (held_px, flush_pixels).
+// Global linear scenes: object records stream through per-wave LDS buffers
+// (stream_objects), or in the brute-force build (RT_CULL=0) through scalar
+// loads in kind runs, where SHADOW_CHECK is how often (in objects) a shadow run
+// asks the wave-level "any ray open?" question.
+enum { SCH = 32 };  // objects per stream chunk: SCH * GEO * 8 B + SCH * 4 B per wave
+enum { SHADOW_CHECK = 8 };
 enum { ST_SHADOW = 0, ST_TRACED = 1, ST_SHADED = 2, ST_SURFERR = 3, ST_STESTS = 4, ST_COUNT = ST_STESTS + RT_NUM_KINDS,
        ST_PHASE = 16, N_PHASE = 10, ST_BVHDIAG = 26, ST_EXDIAG = 34, ST_SHDIAG = 48, ST_PASSDIAG = 54,
        ST_CLOCKSTEP = 60, ST_LANEDIAG = 61 /* 61: lanes waiting in S_DONE, summed over rounds; 62: rounds */,
@@ -191,10 +184,7 @@ enum { SH_POST_S = 0, SH_POST_T = 1, SH_CLAIM = 2, SH_RECLAIM = 3, SH_WAIT = 4, 
 #define SHDIAG(k) (void)0
 #endif  // (stats buffer: 64 entries)
 enum { S_IDLE = 0, S_TRACE = 1, S_SHADE = 2, S_DONE = 3 };  // S_DONE: sample colour held for the quad
-#ifndef RT_LDS_MAX
-#define RT_LDS_MAX (40 * 1024)
-#endif
-enum { LDS_MAX_BYTES = RT_LDS_MAX };
+enum { LDS_MAX_BYTES = 40 * 1024 };  // scene blobs up to this size are staged in LDS
 // PCG jump table entries: (row within the 20-row strip) x (sample 0..3)
 enum { JUMP_ENTRIES = 20 * 4 };
 
@@ -362,19 +352,11 @@ __device__ __forceinline__ RecN<N> ld_rec(PT p) {
   return r;
 }
 // Specialised LDS scenes: object i's geo record (GEO doubles) through scalar
-// loads from the global blob instead of LDS (RT_SPEC_SGEO): the loop over
+// loads from the global blob instead of LDS (sgeo in the kernel): the loop over
 // objects is unrolled, so the record lands in SGPRs and feeds the culls and
 // the FP64 transform as scalar operands (C3 spec: LDS reads 266 -> 106 in the
 // ISA; same-box serial frames C3 -3.0 %, c3cone -2.1 %, C2 -1.7 %,
-// profiles/r04/sgeo/). RT_SPEC_SLIGHTS does the same for the lights, the
-// frame constants and the plane culls' records (all kernels): no further gain
-// on C3, c4csg +1.5 % -- off.
-#ifndef RT_SPEC_SGEO
-#define RT_SPEC_SGEO 1
-#endif
-#ifndef RT_SPEC_SLIGHTS
-#define RT_SPEC_SLIGHTS 0
-#endif
+// profiles/r04/sgeo/).
 // A BVH leaf object's record (bvh_geo: GEO doubles in leaf order; 0..11
 // WorldToObject, 12..13 the FP32 bounding sphere, 14 index, 15 kind) read
 // through the constant address space: the index is wave-uniform, so this is
@@ -383,9 +365,6 @@ struct LeafRec {
   RecN<12> R;
   float cx, cy, cz, cr;
   int i, k;
-#if RT_AXIS_LEAF
-  bool ax;  // a scale + translation sphere (host: axis_sphere)
-#endif
 };
 template <typename PT>
 __device__ __forceinline__ LeafRec ld_leaf_p(PT p) {
@@ -397,10 +376,7 @@ __device__ __forceinline__ LeafRec ld_leaf_p(PT p) {
   L.cz = __int_as_float((int)(uint32_t)b1);
   L.cr = __int_as_float((int)(uint32_t)(b1 >> 32));
   const uint64_t b2 = (uint64_t)__double_as_longlong(p[14]);
-  L.i = (int)(uint32_t)b2;
-#if RT_AXIS_LEAF
-  L.ax = (uint32_t)(b2 >> 32) != 0;
-#endif
+  L.i = (int)(uint32_t)b2;  // (the high word, the host's axis_sphere flag, is not read by any kernel)
   L.k = (int)(uint32_t)(uint64_t)__double_as_longlong(p[15]);
   return L;
 }
@@ -442,17 +418,14 @@ __device__ __forceinline__ void scan_records(cdptr base, int r0, int rn, Body&& 
 
 // body(i, tx, ty, tz) for the uniform-scale spheres i = r0 .. r0 + rn - 1 in
 // index order (urec records, UNI_REC doubles: the translations m3 m7 m11):
-// G records per scalar load group (pairs: 64 B; quads: 128 B), two groups in
-// flight as in scan_records -- 2G spheres tested per wait instead of one, so
-// the record latency hides behind more FP64 work (brute-force C5 band 1.85 ->
-// 1.55 s with pairs). Loads may read up to 2G - 1 records past the run (the
+// G records per scalar load group (quads: 128 B), two groups in flight as in
+// scan_records -- 2G spheres tested per wait instead of one, so the record
+// latency hides behind more FP64 work (brute-force C5 band 1.85 -> 1.55 s
+// with pairs already). Loads may read up to 2G - 1 records past the run (the
 // host pads urec with 8); only indices < r0 + rn reach the body. stop()
 // (wave-uniform) is asked every CHECK objects (a multiple of 2G).
-#ifndef RT_UNI_PAIRS
-// quads: C5 band 1.446-1.455 -> 1.385-1.393 s once no sphere test reloads a
-// spill (before that, pairs and quads measured alike; profiles/r05/unigroup_ab/)
-#define RT_UNI_PAIRS 2
-#endif
+// Quads: C5 band 1.446-1.455 -> 1.385-1.393 s against pairs once no sphere
+// test reloads a spill (profiles/r05/unigroup_ab/).
 // after_rec for scan_uni's 16-dword groups: the dependency goes through a
 // readfirstlane of the record's first dword. Under SGPR pressure (3 lights)
 // the compiler kept a group in VGPRs, and the asm's "s" operand then needed
@@ -466,9 +439,8 @@ __device__ __forceinline__ cdptr after_rec_u(cdptr next, const RecN<N>& cur) {
 }
 template <int CHECK, typename Body, typename Stop>
 __device__ __forceinline__ void scan_uni(cdptr base, int r0, int rn, Body&& body, Stop&& stop) {
-  // G records per load group (RT_UNI_PAIRS = 1: pairs, 2: quads), two groups
-  // in flight
-  constexpr int G = RT_UNI_PAIRS >= 2 ? 4 : 2, ND = G * UNI_REC;
+  // G records per load group (quads), two groups in flight
+  constexpr int G = 4, ND = G * UNI_REC;
   static_assert(UNI_REC == 4 && CHECK % (2 * G) == 0, "scan_uni: 4-double records, stop() at group boundaries");
   cdptr p = base + (size_t)r0 * UNI_REC;
   RecN<ND> A = ld_rec<ND>(p);  // records j .. j + G - 1
@@ -494,18 +466,6 @@ __device__ __forceinline__ void scan_uni(cdptr base, int r0, int rn, Body&& body
   }
 }
 
-// True when q = num/den (den != 0, finite) is certainly <= 0, i.e. num == 0
-// or the signs differ, so the reference would reject t = q (t <= 0) and the
-// division can be skipped. NaN operands return false (the division runs and
-// the NaN flows through exactly as in the reference).
-__device__ __forceinline__ bool t_nonpos(double num, double den) {
-#if RT_DIV_SKIP
-  return (num == 0.0 && !__builtin_isnan(den)) || (num < 0.0 && den > 0.0) || (num > 0.0 && den < 0.0);
-#else
-  return false;
-#endif
-}
-
 // Sphere.Intersect (raytracer.go:58-104): unit sphere, near root only.
 // c = O.O - 1 depends on the ray origin only (shared by the shadow rays of a
 // hit, see shadow_sweep); sphere_hit forms it.
@@ -517,7 +477,6 @@ __device__ __forceinline__ bool sphere_hit_c(const Ray& l, double c, double& t) 
   if (disc < 0.0) return false;
   double sq = gsqrt(disc);
   double num = -hb - sq;
-  if (t_nonpos(num, a)) return false;  // t0 <= 0: no near hit
   double t0 = num / a;
   if (t0 > 0.0) {
     t = t0;
@@ -533,7 +492,6 @@ __device__ __forceinline__ bool plane_hit_c(const Ray& l, d3 n, double pd, doubl
   double denom = dot(n, l.d);
   if (__builtin_fabs(denom) < 1e-6) return false;
   double num = -pd - no;
-  if (t_nonpos(num, denom)) return false;
   double tt = num / denom;
   if (tt <= 0.0) return false;
   t = tt;
@@ -546,9 +504,8 @@ __device__ __forceinline__ bool plane_hit(const Ray& l, d3 n, double pd, double&
 // Cube.Intersect (raytracer.go:214-240) over prim.PlanesForUnitCube
 // (internal/prim/plane.go:29-38). Every face re-transforms the ray with the
 // same matrix in the reference, so one transform gives identical values.
-// With RT_CUBE_FAST the face planes' dot products are evaluated on the one
-// non-zero axis: for a finite ray, n.v = (0*a + 0*b) + (+-1)*c equals +-c
-// exactly whenever c != 0, and when c == 0 both forms are a zero that is
+// The face planes' dot products are evaluated on the one non-zero axis: for
+// a finite ray, n.v = (0*a + 0*b) + (+-1)*c equals +-c exactly whenever c != 0, and when c == 0 both forms are a zero that is
 // rejected identically (|denom| < 1e-6, or t = 0 <= 0), so hits, T and
 // PointObj are bit-identical to the generic dot products.
 __device__ __forceinline__ bool cube_face(const Ray& l, int f, double& best, int& bf, bool& found) {
@@ -562,7 +519,6 @@ __device__ __forceinline__ bool cube_face(const Ray& l, int f, double& best, int
   if (__builtin_fabs(denom) < 1e-6) return false;
   double nO = pos ? oA : -oA;
   double num = negD - nO;
-  if (t_nonpos(num, denom)) return false;
   double tt = num / denom;
   if (tt <= 0.0) return false;
   d3 p = add(l.o, scale(l.d, tt));
@@ -579,26 +535,8 @@ __device__ __forceinline__ bool cube_hit(const Ray& l, double& t, int& face) {
   bool found = false;
   double best = 0.0;
   int bf = 0;
-#if RT_CUBE_FAST
 #pragma unroll
   for (int f = 0; f < 6; f++) cube_face(l, f, best, bf, found);
-#else
-  const double N[6][3] = {{0, 0, -1}, {0, 0, 1}, {-1, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, -1, 0}};
-  const double D[6] = {-0.0, -1.0, -0.0, -1.0, -1.0, -0.0};
-#pragma unroll
-  for (int f = 0; f < 6; f++) {
-    double ft;
-    if (!plane_hit(l, mk(N[f][0], N[f][1], N[f][2]), D[f], ft)) continue;
-    if (ft < 0.0) continue;
-    d3 p = add(l.o, scale(l.d, ft));
-    if (p.x < 0 || p.x > 1 || p.y < 0 || p.y > 1 || p.z < 0 || p.z > 1) continue;
-    if (!found || ft < best) {
-      found = true;
-      best = ft;
-      bf = f;
-    }
-  }
-#endif
   if (found) {
     t = best;
     face = bf;
@@ -631,49 +569,40 @@ __device__ __forceinline__ bool quadric_hit_c(const Ray& l, double c0, double& t
     double disc = hb * hb - a * c0;
     if (disc >= 0.0) {
       double sq = gsqrt(disc);
-      // consider() ignores t <= 0 (raytracer.go:287), so a root whose sign is
-      // known to be non-positive needs no division.
+      // consider() ignores t <= 0 (raytracer.go:287)
       double n0 = -hb - sq, n1 = -hb + sq;
-      if (!t_nonpos(n0, a)) {
-        double t0 = n0 / a;
-        double y0 = l.o.y + l.d.y * t0;
-        if (y0 >= 0.0 && y0 <= 1.0 && t0 > 0.0 && t0 < bestT) {
-          bestT = t0;
-          bestFace = 0;
-        }
-      }
-      if (!t_nonpos(n1, a)) {
-        double t1 = n1 / a;
-        double y1 = l.o.y + l.d.y * t1;
-        if (y1 >= 0.0 && y1 <= 1.0 && t1 > 0.0 && t1 < bestT) {
-          bestT = t1;
-          bestFace = 0;
-        }
-      }
-    }
-  } else if (cone && __builtin_fabs(hb) > 1e-12) {  // cone: ray parallel to a generator
-    double n0 = -c0, den = 2.0 * hb;
-    if (!t_nonpos(n0, den)) {
-      double t0 = n0 / den;
+      double t0 = n0 / a;
       double y0 = l.o.y + l.d.y * t0;
       if (y0 >= 0.0 && y0 <= 1.0 && t0 > 0.0 && t0 < bestT) {
         bestT = t0;
         bestFace = 0;
       }
+      double t1 = n1 / a;
+      double y1 = l.o.y + l.d.y * t1;
+      if (y1 >= 0.0 && y1 <= 1.0 && t1 > 0.0 && t1 < bestT) {
+        bestT = t1;
+        bestFace = 0;
+      }
+    }
+  } else if (cone && __builtin_fabs(hb) > 1e-12) {  // cone: ray parallel to a generator
+    double n0 = -c0, den = 2.0 * hb;
+    double t0 = n0 / den;
+    double y0 = l.o.y + l.d.y * t0;
+    if (y0 >= 0.0 && y0 <= 1.0 && t0 > 0.0 && t0 < bestT) {
+      bestT = t0;
+      bestFace = 0;
     }
   }
   if (__builtin_fabs(l.d.y) > 1e-12) {
     double nTop = 1.0 - l.o.y;
-    if (!t_nonpos(nTop, l.d.y)) {
-      double tTop = nTop / l.d.y;
-      double px = l.o.x + l.d.x * tTop, pz = l.o.z + l.d.z * tTop;
-      if (px * px + pz * pz <= 1.0 && tTop > 0.0 && tTop < bestT) {
-        bestT = tTop;
-        bestFace = 1;
-      }
+    double tTop = nTop / l.d.y;
+    double px = l.o.x + l.d.x * tTop, pz = l.o.z + l.d.z * tTop;
+    if (px * px + pz * pz <= 1.0 && tTop > 0.0 && tTop < bestT) {
+      bestT = tTop;
+      bestFace = 1;
     }
     double nBot = -l.o.y;
-    if (!cone && !t_nonpos(nBot, l.d.y)) {
+    if (!cone) {
       double tBot = nBot / l.d.y;
       double px = l.o.x + l.d.x * tBot, pz = l.o.z + l.d.z * tBot;
       if (px * px + pz * pz <= 1.0 && tBot > 0.0 && tBot < bestT) {
@@ -830,16 +759,13 @@ struct WaveStack {
     sp++;
   }
 };
-// Binary BVH step with the first child kept in registers (RT_BVH_CONT): the
+// Binary BVH step with the first child kept in registers: the
 // child the stack order would pop next is visited directly and only the other
 // is pushed, so a descent skips the LDS store and reload between a node and
 // its first child. Nodes are visited in the same order as with two pushes.
 // Same-box serial frames: C5 119.7 -> 113.5 ms, C4 4.11 -> 4.05 ms
 // (profiles/r04/bvhv/; measured before the far-origin shift it was lost in
 // C5's tail).
-#ifndef RT_BVH_CONT
-#define RT_BVH_CONT 1
-#endif
 __device__ __forceinline__ void bvh_next(WaveStack& st, int& sp, int lane, bool c1_first, int r0, int r1, uint64_t m0,
                                          uint64_t m1, int& nr, uint64_t& nm, bool& have) {
   const int fr = c1_first ? r1 : r0, sr = c1_first ? r0 : r1;
@@ -864,9 +790,6 @@ __device__ __forceinline__ void bvh_next(WaveStack& st, int& sp, int lane, bool 
 // misses that box takes no part. Objects lie in the box, so every cull that
 // could pass for o passes for o' (both conservative); the exact tests still
 // use the reference's ray, so hits and counters do not change.
-#ifndef RT_FAR_SHIFT
-#define RT_FAR_SHIFT 1
-#endif
 __device__ __forceinline__ void far_shift(bool& act, const Ray& r, const double* lo, const double* hi, F3& of,
                                           float& slack, double& t0) {
   if (!RT_FAR_SHIFT || !wave_any(act && slack > 1e-3f)) return;
@@ -1051,21 +974,12 @@ __device__ __forceinline__ void leaf_interval(int kind, DP g, const Ray& r, doub
 // RT_CSG_MAX_LEAVES).
 enum { RT_CSG_ANY = -4, RT_CSG_ALL = -5 };
 // composites with at least this many leaves get spatial leaf groups (host)
-#ifndef RT_CSG_GROUP_MIN
-#define RT_CSG_GROUP_MIN 16
-#endif
-enum { CSG_GROUP_MIN = RT_CSG_GROUP_MIN };
+enum { CSG_GROUP_MIN = 16 };
 // The composite search's wave-uniform reads (postfix program, leaf groups,
 // leaf kinds and records) through scalar loads from the global blob instead
 // of LDS (c4csg serial, same box: 15.33 -> 14.68 ms; the composite's fields
 // made wave-uniform with readfirstlane first: 16.32 -> 15.33 ms, VGPR spills
 // of the CSG quads kernel 95 -> 60; profiles/r04/csg/ab_c4csg_scalar.log)
-#ifndef RT_CSG_SCALAR
-#define RT_CSG_SCALAR 1
-#endif
-#ifndef RT_CSG_FAR
-#define RT_CSG_FAR 1  // far-origin shift of the composite search's culls (csg_hit)
-#endif
 template <typename IP>
 __device__ __forceinline__ bool csg_eval(IP code, int n, uint64_t m0, uint64_t m1) {
   uint64_t st0 = 0, st1 = 0;
@@ -1192,13 +1106,11 @@ __device__ unsigned long long g_csg_diag[8];  // diagnostic build: searches, ove
 #define RT_CSG_DIAG g_csg_diag
 #endif
 // The same search over a register-resident list of the live leaves (at most
-// RT_CSG_LIVE per lane, ascending leaf order, so every tie breaks as above):
+// CSG_LIVE per lane, ascending leaf order, so every tie breaks as above):
 // a ray meets only a few of a composite's leaves, and the per-lane interval
 // arrays of csg_hit_all live in scratch memory. A lane with more live leaves
 // redoes the search with csg_hit_all (identical result).
-#ifndef RT_CSG_LIVE
-#define RT_CSG_LIVE 6  // 0: always the scratch-array search
-#endif
+enum { CSG_LIVE = 6 };
 template <bool CL, typename DP, typename IP, typename GP>
 __device__ __forceinline__ bool csg_hit_all_call(DP geo, IP kinds, IP code, int nobj,
                                               GP g, const Ray& r, double& t, int& face, double cut_m,
@@ -1217,8 +1129,7 @@ template <bool CL, typename DP, typename IP, typename GP>
 __device__ __forceinline__ bool csg_hit(DP geo, IP kinds, IP code, int nobj,
                                         GP g, const Ray& r, double& t, int& face, double cut_m = 1.0,
                                         double cut_lim = __builtin_inf(), bool cut_strict = true) {
-  constexpr int K = RT_CSG_LIVE > 0 ? RT_CSG_LIVE : 1;
-  if constexpr (RT_CSG_LIVE == 0) return csg_hit_all<CL>(geo, kinds, code, nobj, g, r, t, face, cut_m, cut_lim, cut_strict);
+  constexpr int K = CSG_LIVE;
   const auto ci = as_i(g + 14);
   // (the composite's fields are wave-uniform: readfirstlane keeps the reads
   // below them scalar)
@@ -1239,7 +1150,7 @@ __device__ __forceinline__ bool csg_hit(DP geo, IP kinds, IP code, int nobj,
   // to the composite, so no membership change (hit) lies before t0, and a
   // leaf the shifted segment cannot reach holds no point beyond it.
   double tc = 0.0;
-  if (RT_CSG_FAR && slack > 1e-3f) {
+  if (slack > 1e-3f) {
     const auto cb = as_f(g + 12);
     if (cb[3] < 3.0e38f) {
       const double dd = dot(r.d, r.d);
@@ -1526,23 +1437,10 @@ enum { PK_SLOT = 8, PK_MAT = 32 };
 // SIMD) the board's code costs C3 ~10 % in every round (spills, +5 % VALU and
 // +13 % SALU instructions, PMC), more than the tail gains; rt_set_work_sharing
 // compiles it into a context's specialised kernel.
-#ifndef RT_SHARE
-#define RT_SHARE 0
-#endif
-#ifdef RT_COST_MAP
-#undef RT_SHARE
-#define RT_SHARE 0  // the cost-map diagnostic charges a pixel's work to its own lane
-#endif
-#ifndef RT_SHARE_SPINS
-#define RT_SHARE_SPINS (1 << 16)  // idle rounds (s_sleep'd) a drained wave waits for work before leaving
-#endif
-#ifndef RT_SHARE_SLEEP
-#define RT_SHARE_SLEEP 127  // s_sleep per idle round (x64 cycles): a polling wave keeps the issue slots of
-                            // other workgroups' waves on its SIMD almost free
-#endif
-#ifndef RT_SHARE_SAMPLES
-#define RT_SHARE_SAMPLES 1  // post unstarted samples (serial schedule), not only refraction subtrees
-#endif
+enum { SHARE_SPINS = 1 << 16,  // idle rounds (s_sleep'd) a drained wave waits for work before leaving
+       SHARE_SLEEP = 127,      // s_sleep per idle round (x64 cycles): a polling wave keeps the issue slots of
+                               // other workgroups' waves on its SIMD almost free
+       SHARE_SAMPLES = 1 };    // post unstarted samples (serial schedule), not only refraction subtrees
 enum { NSLOT = 64, SLOTS_PER_WAVE = NSLOT / WAVES_PER_WG, S_WAIT = 4, S_RESUME = 5 };
 // S_ADV (serial samples): the lane finished a sample (its colour added to sum);
 // the next one is chosen at the top of the main loop (advance_sample), in one
@@ -1638,20 +1536,15 @@ __device__ __forceinline__ uint64_t low_bits(uint64_t m, int n) {
 // the child's colour at its own frame exactly as it would its own (the
 // reference's per-level clamp, raytracer.go:557-561).
 // ---------------------------------------------------------------------------
-#ifndef RT_GS_MIN_LEVELS
-#define RT_GS_MIN_LEVELS 3  // post only refraction children with >= this many levels below them
-#endif
-// Sharded by XCD (RT_GS_SHARDS rings; a workgroup posts to ring blockIdx mod
+enum { GS_MIN_LEVELS = 3 };  // post only refraction children with >= this many levels below them
+// Sharded by XCD (GS_SH rings; a workgroup posts to ring blockIdx mod
 // shards -- blocks are dealt round-robin over the 8 XCDs, so a ring's posters
 // share an L2 and a memory path; placement only affects speed): each ring
 // has its own head / tail words, and the idle-lane count is replicated per
 // shard (an update adds to every replica, one wave instruction with a lane
 // per replica), so a busy wave's poll reads words only its shard's waves read.
-#ifndef RT_GS_SHARDS
-#define RT_GS_SHARDS 8
-#endif
 enum { GS_FREE = 0, GS_POSTED = 1, GS_CLAIMED = 2, GS_DONE = 3, GS_REC = 8 /* u64 per slot */,
-       GS_RING = 1 << 20 /* ring entries (u64), all shards */, GS_SH = RT_GS_SHARDS,
+       GS_RING = 1 << 20 /* ring entries (u64), all shards */, GS_SH = 8,
        GS_RSH = GS_RING / GS_SH /* entries per shard's ring */,
        // control block (u64 indices; the words 4 KB apart, so no two share a
        // memory channel): shard k's ring head / tail at GS_SHARD * k + 0 / 512,
@@ -1659,16 +1552,7 @@ enum { GS_FREE = 0, GS_POSTED = 1, GS_CLAIMED = 2, GS_DONE = 3, GS_REC = 8 /* u6
        GS_SHARD = 1024, GS_HEAD = 0, GS_TAIL = 512, GS_SET = GS_SHARD * GS_SH /* set s at GS_SET + GS_SETSZ * s */,
        GS_ACTIVE = 0, GS_HELPERS = 512, GS_NIDLE = 1024 /* + 512 * shard */, GS_SETSZ = 1024 + 512 * GS_SH,
        GS_CTL_U64 = GS_SET + 2 * GS_SETSZ };
-static_assert(GS_SH >= 1 && GS_SH <= 32 && (GS_RING % GS_SH) == 0 && (GS_RSH & (GS_RSH - 1)) == 0, "RT_GS_SHARDS");
-#ifndef RT_GS_POLL
-// a busy wave reads the board's words every (RT_GS_POLL + 1)-th round
-// (c4csg 8-rank share, profiles/r05/gpoll: 1.77-1.79 ms at 3, 1.77-1.81 at
-// 1, 1.83 at 0, 1.95 at 15; sharded rings make frequent polls cheap)
-#define RT_GS_POLL 3
-#endif
-#ifndef RT_GS_HELPERS
-#define RT_GS_HELPERS 16  // drained waves that stay to help (device-wide); the others leave at once
-#endif
+static_assert(GS_SH >= 1 && GS_SH <= 32 && (GS_RING % GS_SH) == 0 && (GS_RSH & (GS_RSH - 1)) == 0, "GS_SH");
 #define RT_AG_SCOPE __HIP_MEMORY_SCOPE_AGENT
 __device__ __forceinline__ uint64_t gs_ld(uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, RT_AG_SCOPE); }
 __device__ __forceinline__ void gs_st(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, RT_AG_SCOPE); }
@@ -1900,15 +1784,12 @@ struct View {
 // with it; launch() takes the second set only for a scene that has a cone
 // leaf or an extension opcode. Specialised builds name four arguments: there
 // spec_kind / spec_feat fold away what the scene lacks.
+// Waves per SIMD the register budget is set for: 3 (168 VGPRs; C3 on par with
+// 4; C2 -10%, C4 (BVH) -4%), or 5 in the brute-force build (scalar-load sweep:
+// C5 band -7..-14 % vs 3, profiles/r02/minwaves_ab).
+enum { MIN_WAVES = RT_CULL ? 3 : 5 };
 template <bool LDS, bool BVH, bool CSG, bool QUADS, bool EXT = true>
-#ifndef RT_MIN_WAVES
-#if RT_CULL
-#define RT_MIN_WAVES 3  // 168 VGPRs -> 3 waves/SIMD (C3 on par with 4; C2 -10%, C4 (BVH) -4%)
-#else
-#define RT_MIN_WAVES 5  // brute force (scalar-load sweep): 5 waves/SIMD, C5 band -7..-14 % vs 3 (profiles/r02/minwaves_ab)
-#endif
-#endif
-__global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char* __restrict__ blob, Params P) {
+__global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __restrict__ blob, Params P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef RT_COST_MAP
   constexpr bool QD = false;  // the cost-map diagnostic charges all of a pixel's work to one lane
@@ -1918,7 +1799,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   constexpr bool PR = !QUADS && RT_PAIRS && RT_SHARE != 1;  // pixel pairs (the workgroup board assumes one owner lane)
 #endif
   // pixels per dequeue: 16 quads, 32 pairs (an 8x4 half tile) or 64 pixels
-  constexpr unsigned int QCHUNK = QD ? 16u : PR ? 32u : (unsigned int)RT_QCHUNK_PIXEL;
+  constexpr unsigned int QCHUNK = QD ? 16u : PR ? 32u : (unsigned int)QCHUNK_PIXEL;
   const char* base;
   // Stage the scene (LDS flavour) once per workgroup (the only block-wide
   // barrier).
@@ -1988,13 +1869,8 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   S.shade = reinterpret_cast<const double*>(base + P.off_shade);
   S.mats = reinterpret_cast<const double*>(base + P.off_mats);
   // lights section: a 16-double record of per-frame constants, then the lights
-#if RT_SPEC_SLIGHTS
-  const cdptr G = (cdptr)(blob + P.off_lights);
-  S.lights = reinterpret_cast<const double*>(base + P.off_lights) + GLOB;
-#else
   const double* G = reinterpret_cast<const double*>(base + P.off_lights);
   S.lights = G + GLOB;
-#endif
   S.kind = reinterpret_cast<const int*>(base + P.off_kind);
   S.objmat = reinterpret_cast<const int*>(base + P.off_objmat);
   S.pref = reinterpret_cast<const uint32_t*>(base + P.off_pref);
@@ -2002,30 +1878,17 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   S.code = reinterpret_cast<const uint32_t*>(base + P.off_code);
   S.entry = reinterpret_cast<const int*>(base + P.off_entry);
   S.consts = reinterpret_cast<const uint64_t*>(base + P.off_consts);
-#if RT_SPEC_SGEO && defined(RT_SPEC_NOBJ)
+#ifdef RT_SPEC_NOBJ
   const cdptr sgeo = (cdptr)(blob + P.off_geo);  // object records through scalar loads
 #endif
-#if RT_CSG_SCALAR
   // composite programs, leaf groups and leaf records through scalar loads
   const cdptr cs_geo = (cdptr)(blob + P.off_geo);
   const ciptr cs_kind = (ciptr)(blob + P.off_kind);
   const ciptr cs_csg = (ciptr)(blob + P.off_csg);
 #define CSG_ARGS cs_geo, cs_kind, cs_csg
 #define CSG_G(i, g) (cs_geo + (size_t)(i) * GEO)
-#else
-#define CSG_ARGS S.geo, S.kind, S.csg
-#define CSG_G(i, g) (g)
-#endif
-#if RT_SPEC_SLIGHTS
-  // wave-uniform records through scalar loads: lights, plane culls
-  const cdptr slights = G + GLOB;
-  const cdptr sshade = (cdptr)(blob + P.off_shade);
-#define LTP(li) (slights + (size_t)(li) * LGT)
-#define SHP(i) (sshade + (size_t)(i) * SHD)
-#else
 #define LTP(li) (S.lights + (size_t)(li) * LGT)
 #define SHP(i) (S.shade + (size_t)(i) * SHD)
-#endif
 
   const int lane = (int)(threadIdx.x & 63);
   const int wslot = (int)(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6));
@@ -2062,7 +1925,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   // the next chunk's 16-B loads in flight while the current chunk is tested
   // (the in-order loop the reference runs, with the record latency hidden).
   // body(i, kind, record) returns false to stop (a wave-uniform decision).
-  constexpr bool STREAM = !LDS && !BVH && !CSG && RT_STREAM;
+  constexpr bool STREAM = !LDS && !BVH && !CSG;
   double* sbuf = reinterpret_cast<double*>(smem + P.stream_off) + (size_t)(threadIdx.x >> 6) * (SCH * GEO);
   int* skind = reinterpret_cast<int*>(smem + P.stream_off + WAVES_PER_WG * SCH * GEO * (int)sizeof(double)) +
                (threadIdx.x >> 6) * SCH;
@@ -2095,26 +1958,8 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
       const int n = min(SCH, P.nobj - c0);
       const bool more = c0 + SCH < P.nobj;
       if (more) fetch(c0 + SCH);
-#if RT_STREAM_PREFETCH
-      // record j + 1 read from LDS while record j is tested (registers)
-      double rec[GEO], nxt[GEO];
-#pragma unroll
-      for (int q = 0; q < GEO; q++) rec[q] = sbuf[q];
-      int kc = skind[0];
-      for (int j = 0; j < n; j++) {
-        const int jn = j + 1 < n ? j + 1 : j;
-#pragma unroll
-        for (int q = 0; q < GEO; q++) nxt[q] = sbuf[(size_t)jn * GEO + q];
-        const int kn = skind[jn];
-        if (!body(c0 + j, kc, rec)) return;
-#pragma unroll
-        for (int q = 0; q < GEO; q++) rec[q] = nxt[q];
-        kc = kn;
-      }
-#else
       for (int j = 0; j < n; j++)
         if (!body(c0 + j, skind[j], sbuf + (size_t)j * GEO)) return;
-#endif
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // every lane done reading the chunk
       if (more) store();
     }
@@ -2127,7 +1972,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   int px = 0, py = 0, sample = 0, sp = 0;
   unsigned int pout = 0;  // output pixel index
   // Finished pixel held for the wave's next batched framebuffer store
-  // (RT_PIX_BATCH): index (~0u = none) and RGBA8 value.
+  // (see the framebuffer stores note at SCH): index (~0u = none) and RGBA8 value.
   uint32_t held_px = ~0u, held_val = 0u;
   // One store instruction for every lane's held pixel (wave-uniform call).
   auto flush_pixels = [&]() {
@@ -2135,12 +1980,10 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
     held_px = ~0u;
   };
   // work sharing (RT_SHARE): per-lane sample bookkeeping in Bd->lw (Board)
-// the wave index through readfirstlane (an SGPR) in the BVH and CSG kernels:
-// C4 -1.0 %, c4csg -2.2 %; C3 +0.5..1.2 %, C2 +1.3..2.2 % (profiles/r05/wave_ab/)
-#ifndef RT_WAVE_SGPR
-#define RT_WAVE_SGPR (BVH || CSG)
-#endif
-  const int wave = RT_WAVE_SGPR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
+  // the wave index through readfirstlane (an SGPR) in the BVH and CSG kernels:
+  // C4 -1.0 %, c4csg -2.2 %; C3 +0.5..1.2 %, C2 +1.3..2.2 % (profiles/r05/wave_ab/)
+  constexpr bool WAVE_SGPR = BVH || CSG;
+  const int wave = WAVE_SGPR ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
   int my_idle = 0, spins = 0;  // wave-uniform: idle lanes this wave reports, idle rounds
   bool my_active = true;       // wave-uniform: counted in Bd->nactive
   // wave-uniform: the tail has begun for this wave (it drained the queue, or
@@ -2169,9 +2012,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   // spilled, and each pass paid a scratch reload and a vmcnt(0) wait per
   // counter. C4 -1.0 %, c4csg -0.9 %; the small linear scenes (C3 within
   // noise, C2 +2 %) keep the plain form (profiles/r05/remat_ab/).
-#ifndef RT_CNT_REMAT
-#define RT_CNT_REMAT (BVH || CSG)
-#endif
+  constexpr bool CNT_REMAT = BVH || CSG;
   auto opaque_s = [](uint32_t b) {  // (b is wave-uniform: readfirstlane makes that explicit)
     b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
     asm volatile("" : "+s"(b));
@@ -2179,7 +2020,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   };
   // shadow tests of kind k (per lane): kcnt[k * WG + threadIdx.x]
   auto cnt_kind = [&](int k, uint64_t v) {
-    if constexpr (RT_CNT_REMAT) {
+    if constexpr (CNT_REMAT) {
       uint32_t l;  // the lane number from mbcnt at the use (a hoisted one was spilled too)
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
       const uint32_t a = opaque_s((uint32_t)P.cnt_off + (uint32_t)(CNT_KIND_OFF + (k * WG + wave * 64) * 8)) + l * 8u;
@@ -2192,7 +2033,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
   auto cnt_unit = [&](int k, bool b) {
     const unsigned int n = (unsigned int)__popcll(wave_ballot(b));
     if (lane == 0 && n) {
-      if constexpr (RT_CNT_REMAT)
+      if constexpr (CNT_REMAT)
         atomicAdd(reinterpret_cast<unsigned long long*>(
                       smem + opaque_s((uint32_t)P.cnt_off + (uint32_t)((k * WAVES_PER_WG + wave) * 8))),
                   (unsigned long long)n);
@@ -2263,12 +2104,8 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         lane_cost = 0;
 #else
         const uint32_t v = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
-        if (RT_PIX_BATCH) {  // (the S_ADV block flushed a previously held pixel)
-          held_px = pout;
-          held_val = v;
-        } else {
-          P.out[pout] = v;
-        }
+        held_px = pout;  // (the S_ADV block flushed a previously held pixel)
+        held_val = v;
 #endif
         state = S_IDLE;
         return;
@@ -2424,7 +2261,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         // a lane about to finish a pixel while it still holds one: every
         // held pixel goes out in one store first (with sharing a lane may also
         // finish by taking helpers' colours, so any advancing holder flushes)
-        if (RT_PIX_BATCH && wave_any(state == S_ADV && held_px != ~0u && (RT_SHARE || (!PR && sample == 4)))) flush_pixels();
+        if (wave_any(state == S_ADV && held_px != ~0u && (RT_SHARE || (!PR && sample == 4)))) flush_pixels();
         if (state == S_ADV) {
           const uint32_t w = RT_SHARE == 1 ? Bd->lw[threadIdx.x] : 4u;
           if (RT_SHARE == 1 && __builtin_expect(lw_task(w) >= 0, 0)) {
@@ -2451,19 +2288,15 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
           const int lk = (lane + k) & 63;
           sm = add(sm, mk(__shfl(sum.x, lk), __shfl(sum.y, lk), __shfl(sum.z, lk)));
         }
-        if (RT_PIX_BATCH && wave_any(((qd >> lane) & 1) && held_px != ~0u)) flush_pixels();
+        if (wave_any(((qd >> lane) & 1) && held_px != ~0u)) flush_pixels();
         if ((qd >> lane) & 1) {
           const d3 c = scale(sm, 1.0 / 4.0);
           const uint32_t r8 = go_f64_to_u32(c.x * 65535.0) >> 8;
           const uint32_t g8 = go_f64_to_u32(c.y * 65535.0) >> 8;
           const uint32_t b8 = go_f64_to_u32(c.z * 65535.0) >> 8;
           const uint32_t v = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
-          if (RT_PIX_BATCH) {
-            held_px = pout;
-            held_val = v;
-          } else {
-            P.out[pout] = v;
-          }
+          held_px = pout;
+          held_val = v;
         }
         if ((qd >> (lane & ~3)) & 1) state = S_IDLE;
       }
@@ -2480,19 +2313,15 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         const d3 c2 = mk(__shfl(sum.x, lb), __shfl(sum.y, lb), __shfl(sum.z, lb));
         const d3 c3 = mk(__shfl(sum2.x, lb), __shfl(sum2.y, lb), __shfl(sum2.z, lb));
         const d3 sm = add(add(sum, c2), c3);
-        if (RT_PIX_BATCH && wave_any(((pd >> lane) & 1) && held_px != ~0u)) flush_pixels();
+        if (wave_any(((pd >> lane) & 1) && held_px != ~0u)) flush_pixels();
         if ((pd >> lane) & 1) {
           const d3 c = scale(sm, 1.0 / 4.0);
           const uint32_t r8 = go_f64_to_u32(c.x * 65535.0) >> 8;
           const uint32_t g8 = go_f64_to_u32(c.y * 65535.0) >> 8;
           const uint32_t b8 = go_f64_to_u32(c.z * 65535.0) >> 8;
           const uint32_t v = (r8 & 0xffu) | ((g8 & 0xffu) << 8) | ((b8 & 0xffu) << 16) | 0xff000000u;
-          if (RT_PIX_BATCH) {
-            held_px = pout;
-            held_val = v;
-          } else {
-            P.out[pout] = v;
-          }
+          held_px = pout;
+          held_val = v;
         }
         if ((pd >> (lane & ~1)) & 1) state = S_IDLE;
       }
@@ -2510,7 +2339,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
       if (pool_next >= pool_end) {
         const unsigned int nchunks = (P.total_slots + QCHUNK - 1) / QCHUNK;
         unsigned int c = nchunks;
-        const int nheads = gridDim.x >= QHEADS ? min(QHEADS, RT_QSTEAL + 1) : QHEADS;
+        const int nheads = gridDim.x >= QHEADS ? min(QHEADS, QSTEAL + 1) : QHEADS;
         while (qhead < nheads) {
           const unsigned int h = (blockIdx.x + qhead) % QHEADS;
           const unsigned int dm = __builtin_amdgcn_readfirstlane(__atomic_load_n(qdrained, __ATOMIC_RELAXED));
@@ -2647,9 +2476,9 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         const bool busy_lane = state == S_TRACE || state == S_SHADE || state == S_WAIT;
         int L = -1;
         // (a child at level L + 1 roots at most 2^(depth - L - 1) - 1 rays:
-        // only subtrees of RT_GS_MIN_LEVELS levels or more are worth a hand-off)
+        // only subtrees of GS_MIN_LEVELS levels or more are worth a hand-off)
         if (busy_lane)
-          for (int l = min(sp - 1, P.depth - 1 - RT_GS_MIN_LEVELS); l >= 0; l--) {
+          for (int l = min(sp - 1, P.depth - 1 - GS_MIN_LEVELS); l >= 0; l--) {
             const int f = (int)(__double_as_longlong(core_ld(l, 4)) & 0xff);
             if (f & FL_TASK) break;
             if ((f & (FL_HASR | FL_HAST | FL_STAGE | FL_FORKED)) == (FL_HASR | FL_HAST)) L = l;
@@ -2785,7 +2614,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         // would saturate the board's words); a helper leaves once no wave is
         // busy -- a posted or claimed subtree's owner is busy until it has
         // the colour, so then nothing is left to take (stale tickets of
-        // reclaimed slots may remain) -- or after RT_SHARE_SPINS idle rounds
+        // reclaimed slots may remain) -- or after SHARE_SPINS idle rounds
         if (!gs_helper) {
           unsigned int old = 0;
           if (lane == 0) old = atomicAdd(g_helpers, 1u);
@@ -2796,19 +2625,19 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
           }
         }
         const int na = (spins & 7) ? 1 : __builtin_amdgcn_readfirstlane(lane == 0 ? (int)gs_ld32(g_active) : 0);
-        if (na == 0 || ++spins > RT_SHARE_SPINS) {
+        if (na == 0 || ++spins > SHARE_SPINS) {
 #ifdef RT_PHASE_TIMING
           if (lane == 0) atomicAdd(P.stats + ST_SHDIAG + SH_SPIN, (unsigned long long)spins);
 #endif
           if (my_idle) nidle_add(-my_idle);
           break;
         }
-        __builtin_amdgcn_s_sleep(RT_SHARE_SLEEP);
+        __builtin_amdgcn_s_sleep(SHARE_SLEEP);
         continue;
       }
       spins = 0;
       if (__builtin_expect(!wave_any(state == S_TRACE || state == S_SHADE || state == S_RESUME), 0)) {
-        __builtin_amdgcn_s_sleep(RT_SHARE_SLEEP / 4);  // only waiting (or quad-holding) lanes
+        __builtin_amdgcn_s_sleep(SHARE_SLEEP / 4);  // only waiting (or quad-holding) lanes
         continue;
       }
     } else if constexpr (RT_SHARE == 1) {
@@ -2831,7 +2660,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         // shallowest frame whose refraction child is pending and not posted
         // (frames above a claimed subtree's sentinel only)
         const uint32_t w = busy_lane ? Bd->lw[threadIdx.x] : 0u;
-        const bool cs = !QD && RT_SHARE_SAMPLES && busy_lane && lw_task(w) < 0 && lw_own_end(w) - 1 > sample;
+        const bool cs = !QD && SHARE_SAMPLES && busy_lane && lw_task(w) < 0 && lw_own_end(w) - 1 > sample;
         int L = -1;
         if (busy_lane && !cs)
           for (int l = sp - 1; l >= 0; l--) {
@@ -2939,19 +2768,19 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         const uint64_t pm = __hip_atomic_load(&Bd->post, __ATOMIC_RELAXED, RT_WG_SCOPE);
         if ((na == 0 && __builtin_amdgcn_readfirstlane((int)(pm >> 32)) == 0 &&
              __builtin_amdgcn_readfirstlane((int)pm) == 0) ||
-            ++spins > RT_SHARE_SPINS) {
+            ++spins > SHARE_SPINS) {
 #ifdef RT_PHASE_TIMING
           if (lane == 0) atomicAdd(P.stats + ST_SHDIAG + SH_SPIN, (unsigned long long)spins);
 #endif
           if (lane == 0 && my_idle) __hip_atomic_fetch_add(&Bd->nidle, -my_idle, __ATOMIC_RELAXED, RT_WG_SCOPE);
           break;
         }
-        __builtin_amdgcn_s_sleep(RT_SHARE_SLEEP);
+        __builtin_amdgcn_s_sleep(SHARE_SLEEP);
         continue;
       }
       spins = 0;
       if (__builtin_expect(!wave_any(state == S_TRACE || state == S_SHADE || state == S_RESUME), 0)) {  // only waiting (or quad-holding) lanes
-        __builtin_amdgcn_s_sleep(RT_SHARE_SLEEP / 4);
+        __builtin_amdgcn_s_sleep(SHARE_SLEEP / 4);
         continue;
       }
     } else {
@@ -2984,14 +2813,12 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
       long long pf_packed = 0;
       d3 pf_lw = mk(0, 0, 0);
       double pf_kr = 0.0;
-#if RT_FRAME_PREFETCH
       if (tr && sp > 0) {
         pf = true;
         pf_packed = __double_as_longlong(core_ld(sp - 1, 4));
         pf_lw = mk(core_ld(sp - 1, 0), core_ld(sp - 1, 1), core_ld(sp - 1, 2));
         pf_kr = core_ld(sp - 1, 3);
       }
-#endif
       bool found = false;
       double best_t = 0.0;
       int best_i = 0, best_f = 0;
@@ -3039,20 +2866,16 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         {
 #pragma unroll
           for (int i = 0; i < RT_SPEC_NOBJ; i++) {
-#if RT_SPEC_SGEO
-            // (scalar loads, see RT_SPEC_SGEO)
+            // (scalar loads, see ld_rec)
             double gl[GEO];
 #pragma unroll
             for (int q = 0; q < GEO; q++) gl[q] = sgeo[i * GEO + q];
             trace_obj(i, spec_kinds[i], gl, tr);
-#else
-            trace_obj(i, spec_kinds[i], S.geo + (size_t)i * GEO, tr);
-#endif
           }
         }
 #else
         if constexpr (STREAM) {
-#if RT_STREAM_SMEM && !RT_CULL
+#if !RT_CULL
           // Brute force over a global linear scene, in kind runs. A sphere run
           // is a scalar-load loop with the next record in flight: every lane
           // forms the quadratic (Sphere.Intersect, raytracer.go:58-104) and only
@@ -3102,11 +2925,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
                   }
                 }
               };
-              if (RT_UNI_PAIRS)
-                scan_uni<0>((cdptr)P.urec, r0, rn, ubody, [] { return false; });
-              else
-                scan_records<0, 3, UNI_REC>((cdptr)P.urec, r0, rn, [&](int i, const Rec3& R) { ubody(i, R.m[0], R.m[1], R.m[2]); },
-                                            [] { return false; });
+              scan_uni<0>((cdptr)P.urec, r0, rn, ubody, [] { return false; });
             } else if (spec_kind(RT_SPHERE) && rk == RT_SPHERE && rax_k && rax) {
               scan_records<0, 6, AXIS_REC>((cdptr)P.arec, r0, rn, [&](int i, const Rec6& R) {
                 Ray l;
@@ -3143,16 +2962,11 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         double bt0 = 0.0;
         bool btr = tr;
         far_shift(btr, ray, P.bvh_lo, P.bvh_hi, bof, bslack, bt0);
-#if RT_AXIS_LEAF
-        // leaves' scale + translation spheres take the diagonal transform (exact, see axis_o)
-        const bool rax = wave_all(!tr || (axis_o_ok(ray.o) && axis_d_ok(ray.d)));
-#endif
 #ifdef RT_PHASE_TIMING
         bd_trays++;
 #endif
         int ssp = 0;
-#if RT_BVH_CONT
-        int nr = 0;  // the node visited next, kept in registers (see RT_BVH_CONT)
+        int nr = 0;  // the node visited next, kept in registers (see bvh_next)
         uint64_t nm = wave_ballot(btr);
         bool have = true;
         for (;;) {
@@ -3169,14 +2983,6 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
             m = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(bst.mask[ssp] >> 32)) << 32) |
                 (uint32_t)__builtin_amdgcn_readfirstlane((int)bst.mask[ssp]);
           }
-#else
-        bst.push(ssp, lane, 0, wave_ballot(btr));
-        while (ssp > 0) {
-          ssp--;
-          const int r = __builtin_amdgcn_readfirstlane(bst.ref[ssp]);
-          const uint64_t m = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(bst.mask[ssp] >> 32)) << 32) |
-                             (uint32_t)__builtin_amdgcn_readfirstlane((int)bst.mask[ssp]);
-#endif
           const bool act = btr && ((m >> lane) & 1);
 #ifdef RT_PHASE_TIMING
           bd_tnodes++;
@@ -3195,26 +3001,6 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
               const float tmax = found ? (float)(best_t - bt0) * 1.0001f + 1e-4f : 3.0e38f;
               const bool test = may_hit_s(act, bof, df, tmax, L.cx, L.cy, L.cz, L.cr, bslack);
               if (!wave_any(test)) continue;
-#if RT_AXIS_LEAF
-              if (spec_kind(RT_SPHERE) && L.k == RT_SPHERE && L.ax && rax) {
-                // scale + translation sphere: diagonal transform (exact, see axis_o)
-                EXDIAG(RT_SPHERE, 0, test);
-                if (test) {
-                  const double a[6] = {L.R.m[0], L.R.m[3], L.R.m[5], L.R.m[7], L.R.m[10], L.R.m[11]};
-                  Ray l;
-                  l.o = axis_o(a, ray.o);
-                  l.d = axis_d(a, ray.d);
-                  double t;
-                  if (sphere_hit(l, t) && (!found || t < best_t || (t == best_t && L.i < best_i))) {
-                    found = true;
-                    best_t = t;
-                    best_i = L.i;
-                    best_f = 0;
-                  }
-                }
-                continue;
-              }
-#endif
               trace_exact(L.i, L.k, L.R.m, test);
             }
           } else {
@@ -3227,17 +3013,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
             const uint64_t m0 = wave_ballot(a0), m1 = wave_ballot(a1);
             // near child popped first: the one most lanes enter first
             const bool c1_first = 2 * __popcll(wave_ballot(a0 && a1 && t1 < t0)) > __popcll(m0 & m1);
-#if RT_BVH_CONT
             bvh_next(bst, ssp, lane, c1_first, ni[0], ni[1], m0, m1, nr, nm, have);
-#else
-            if (c1_first) {
-              if (m0) bst.push(ssp, lane, ni[0], m0);
-              if (m1) bst.push(ssp, lane, ni[1], m1);
-            } else {
-              if (m1) bst.push(ssp, lane, ni[1], m1);
-              if (m0) bst.push(ssp, lane, ni[0], m0);
-            }
-#endif
           }
         }
       }
@@ -3369,9 +3145,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
     d3 L = mk(0, 0, 0);
     if (hit) L = scale(mk(G[0], G[1], G[2]), M[9]);
     const double rlen = len(ray.d);
-#if RT_STMAX_F32
     const float rlen_rcpf = __builtin_amdgcn_rcpf((float)rlen);
-#endif
     const d3 sorig = add(pw, scale(nw, 1e-4));
 // (hoisting the plane culls' origin half out of the light loop measured
 // +4.6 % on C3, profiles/r05/c3_ab: not kept)
@@ -3404,7 +3178,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
 // (at most 4 lights: with 5-8 the joint sweep's per-light state broke the
 // backend -- "illegal VGPR to SGPR copy", which aborts the process inside
 // hipRTC -- in round 4's code as in this one; scripts/spec_matrix.sh)
-#if RT_STREAM_SMEM && !RT_CULL && RT_SHADOW_JOINT && !defined(RT_SPEC_NOBJ) && RT_SPEC_NLIGHTS <= 4
+#if !RT_CULL && !defined(RT_SPEC_NOBJ) && RT_SPEC_NLIGHTS <= 4
 #define RT_JOINT_SWEEP 1
 #else
 #define RT_JOINT_SWEEP 0
@@ -3495,18 +3269,13 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
               }
             }
           };
-          if (RT_UNI_PAIRS)
-            scan_uni<RT_SHADOW_CHECK>((cdptr)P.urec, r0, rn, ubody, [&] { return !refresh(); });
-          else
-            scan_records<RT_SHADOW_CHECK, 3, UNI_REC>((cdptr)P.urec, r0, rn,
-                                                      [&](int i, const Rec3& R) { ubody(i, R.m[0], R.m[1], R.m[2]); },
-                                                      [&] { return !refresh(); });
+          scan_uni<SHADOW_CHECK>((cdptr)P.urec, r0, rn, ubody, [&] { return !refresh(); });
         } else if (spec_kind(RT_SPHERE) && rk == RT_SPHERE && rax_k && sax) {
-          scan_records<RT_SHADOW_CHECK, 6, AXIS_REC>((cdptr)P.arec, r0, rn, [&](int i, const Rec6& R) {
+          scan_records<SHADOW_CHECK, 6, AXIS_REC>((cdptr)P.arec, r0, rn, [&](int i, const Rec6& R) {
             jsphere(i, axis_o(R.m, sorig), [&](int li) { return axis_d(R.m, ldir_a[li]); });
           }, [&] { return !refresh(); });
         } else if (spec_kind(RT_SPHERE) && rk == RT_SPHERE) {
-          scan_records<RT_SHADOW_CHECK>(cgeo, r0, rn, [&](int i, const Rec12& R) {
+          scan_records<SHADOW_CHECK>(cgeo, r0, rn, [&](int i, const Rec12& R) {
             jsphere(i, to_obj_o(R.m, sorig), [&](int li) { return to_obj_d(R.m, ldir_a[li]); });
           }, [&] { return !refresh(); });
         } else {
@@ -3553,14 +3322,11 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
       const F3 sof = f3(sorig), sdf = f3(ldir);
       const float sslack = ray_slack(sof);
       // occluders must lie within t < dist / |ray.d| (raytracer.go:424)
-#if RT_STMAX_F32
       // FP32 reciprocal instead of an FP64 division: relative error < 4 ulp(f32)
       // ~ 2.4e-7, far inside the 1e-4 margin (NaN / inf cases as in FP64;
-      // dist = 0 culls everything, and nothing can occlude within t*|d| < 0)
+      // dist = 0 culls everything, and nothing can occlude within t*|d| < 0);
+      // C3 -1..-1.7 %
       const float stmax = (float)dist * rlen_rcpf * 1.0001f + 1e-4f;
-#else
-      const float stmax = (float)(dist / rlen) * 1.0001f + 1e-4f;
-#endif
       // inShadow's test count is #{i < end, i != hit} with end = first
       // occluder + 1 (or nobj); counted per kind from the prefix table below.
       int send = P.nobj;
@@ -3575,10 +3341,10 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
 #if defined(RT_SPEC_NLIGHTS) && RT_JOINT_SWEEP
           open = jopen[li];  // the joint sweep above
           send = jsend[li];
-#elif RT_STREAM_SMEM && !RT_CULL
+#elif !RT_CULL
           // Brute force in kind runs (see the TRACE pass); inShadow stops at the
           // first occluder (raytracer.go:411-429), the wave once no lane is open
-          // (tested every RT_SHADOW_CHECK objects: a closed lane never reopens).
+          // (tested every SHADOW_CHECK objects: a closed lane never reopens).
           const cdptr cgeo = (cdptr)S.geo;
           auto ssphere = [&](int i, const Ray& l) {
             const double a = dot(l.d, l.d);
@@ -3610,19 +3376,19 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
               const d3 so = mk(sc * sr.o.x, sc * sr.o.y, sc * sr.o.z);
               Ray l;
               l.d = mk(sc * sr.d.x, sc * sr.d.y, sc * sr.d.z);
-              scan_records<RT_SHADOW_CHECK, 3, UNI_REC>((cdptr)P.urec, r0, rn, [&](int i, const Rec3& R) {
+              scan_records<SHADOW_CHECK, 3, UNI_REC>((cdptr)P.urec, r0, rn, [&](int i, const Rec3& R) {
                 l.o = mk(so.x + R.m[0], so.y + R.m[1], so.z + R.m[2]);
                 ssphere(i, l);
               }, [&] { return !wave_any(open); });
             } else if (spec_kind(RT_SPHERE) && rk == RT_SPHERE && rax_k && sax) {
-              scan_records<RT_SHADOW_CHECK, 6, AXIS_REC>((cdptr)P.arec, r0, rn, [&](int i, const Rec6& R) {
+              scan_records<SHADOW_CHECK, 6, AXIS_REC>((cdptr)P.arec, r0, rn, [&](int i, const Rec6& R) {
                 Ray l;
                 l.o = axis_o(R.m, sr.o);
                 l.d = axis_d(R.m, sr.d);
                 ssphere(i, l);
               }, [&] { return !wave_any(open); });
             } else if (spec_kind(RT_SPHERE) && rk == RT_SPHERE) {
-              scan_records<RT_SHADOW_CHECK>(cgeo, r0, rn, [&](int i, const Rec12& R) { ssphere(i, to_obj(R.m, sr)); },
+              scan_records<SHADOW_CHECK>(cgeo, r0, rn, [&](int i, const Rec12& R) { ssphere(i, to_obj(R.m, sr)); },
                                             [&] { return !wave_any(open); });
             } else {
               for (int i = r0; i < r0 + rn; i++) {
@@ -3664,7 +3430,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
           if (!wave_any(open)) break;
           const int k = S.kind[i];
 #endif
-#if RT_SPEC_SGEO && defined(RT_SPEC_NOBJ)
+#ifdef RT_SPEC_NOBJ
           double gl[GEO];
 #pragma unroll
           for (int q = 0; q < GEO; q++) gl[q] = sgeo[i * GEO + q];
@@ -3738,14 +3504,10 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
         bool sact = hit;
         far_shift(sact, sr, P.bvh_lo, P.bvh_hi, sbof, sbslack, sbt0);
         const float sbtmax = sbt0 == 0.0 ? stmax : (float)(dist / rlen - sbt0) * 1.0001f + 1e-4f;
-#if RT_AXIS_LEAF
-        const bool sax = wave_all(!hit || (axis_o_ok(sr.o) && axis_d_ok(sr.d)));
-#endif
 #ifdef RT_PHASE_TIMING
         bd_srays++;
 #endif
         int ssp = 0;
-#if RT_BVH_CONT
         int nr = 0;
         uint64_t nm = wave_ballot(sact);
         bool have = true;
@@ -3763,14 +3525,6 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
             m = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(bst.mask[ssp] >> 32)) << 32) |
                 (uint32_t)__builtin_amdgcn_readfirstlane((int)bst.mask[ssp]);
           }
-#else
-        bst.push(ssp, lane, 0, wave_ballot(sact));
-        while (ssp > 0) {
-          ssp--;
-          const int r = __builtin_amdgcn_readfirstlane(bst.ref[ssp]);
-          const uint64_t m = ((uint64_t)__builtin_amdgcn_readfirstlane((int)(bst.mask[ssp] >> 32)) << 32) |
-                             (uint32_t)__builtin_amdgcn_readfirstlane((int)bst.mask[ssp]);
-#endif
           const bool act = sact && ((m >> lane) & 1);
 #ifdef RT_PHASE_TIMING
           bd_snodes++;
@@ -3788,21 +3542,6 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
               const bool test = may_hit_s(CULL_AND(CULL_AND(act, L.i != hit_i), L.i < occ), sbof, sdf, sbtmax, L.cx,
                                           L.cy, L.cz, L.cr, sbslack);
               if (!wave_any(test)) continue;
-#if RT_AXIS_LEAF
-              if (spec_kind(RT_SPHERE) && L.k == RT_SPHERE && L.ax && sax) {
-                // scale + translation sphere: diagonal transform (exact, see axis_o)
-                EXDIAG(RT_SPHERE, 1, test);
-                if (test) {
-                  const double a[6] = {L.R.m[0], L.R.m[3], L.R.m[5], L.R.m[7], L.R.m[10], L.R.m[11]};
-                  Ray l;
-                  l.o = axis_o(a, sr.o);
-                  l.d = axis_d(a, sr.d);
-                  double t;
-                  if (sphere_hit(l, t) && t * rlen < dist) occ = L.i;
-                }
-                continue;
-              }
-#endif
               shadow_exact(L.i, L.k, L.R.m, test);
             }
           } else {
@@ -3812,27 +3551,9 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
             const bool a0 = may_hit_box_a(CULL_AND(act, ni[2] < occ), sbof, sidf, sbslack, sbtmax, nb, t0);
             const bool a1 = may_hit_box_a(CULL_AND(act, ni[3] < occ), sbof, sidf, sbslack, sbtmax, nb + 6, t1);
             const uint64_t m0 = wave_ballot(a0), m1 = wave_ballot(a1);
-#ifndef RT_SHADOW_NEAR_FIRST
-#define RT_SHADOW_NEAR_FIRST 0  // measured: near-first shadow order is slower (C5 695 -> 822 ms)
-#endif
-#if RT_SHADOW_NEAR_FIRST
-            // nearer subtree popped first: finds an occluder soonest
-            const bool c1_first = 2 * __popcll(wave_ballot(a0 && a1 && t1 < t0)) > __popcll(m0 & m1);
-#else
             // lower-index subtree popped first: it can prune the other
             const bool c1_first = ni[3] < ni[2];
-#endif
-#if RT_BVH_CONT
             bvh_next(bst, ssp, lane, c1_first, ni[0], ni[1], m0, m1, nr, nm, have);
-#else
-            if (c1_first) {
-              if (m0) bst.push(ssp, lane, ni[0], m0);
-              if (m1) bst.push(ssp, lane, ni[1], m1);
-            } else {
-              if (m1) bst.push(ssp, lane, ni[1], m1);
-              if (m0) bst.push(ssp, lane, ni[0], m0);
-            }
-#endif
           }
         }
         open = hit && occ == 0x7fffffff;
@@ -3957,7 +3678,7 @@ __global__ __launch_bounds__(WG, RT_MIN_WAVES) void rt_render_kernel(const char*
     unwind(have_res, res, false, 0, mk(0, 0, 0), 0.0);
     PH_MARK(9);
   }
-  if (RT_PIX_BATCH) flush_pixels();
+  flush_pixels();
 
   if (lane == 0) {
 #ifdef RT_PHASE_TIMING

@@ -143,7 +143,7 @@ def test_reference_dice_program_renders_through_csg():
 
 def test_far_origin_hits_are_first_membership_changes():
     """Rays starting 150-400 units out (the origins for which the device's
-    composite search shifts its culls, rt_render.h csg_hit RT_CSG_FAR) against
+    composite search shifts its culls, rt_render.h csg_hit) against
     a composite of 20 leaves with a half-space and tied duplicate leaves: the
     oracle's hit is still the first membership change along the ray."""
     rng = random.Random(7)

@@ -240,10 +240,11 @@ def test_surface_vm_matches_interpreter(ctx, name):
 
 
 def test_shared_reciprocal_division_is_bit_exact():
-    """rt_device.h norm() built with RT_FAST_NORM=1 (an off-by-default knob):
-    the shared-reciprocal quotients equal IEEE `/` for ~270M random vectors
-    (safe range, its edges, denormals, specials); most waves take the fast
-    path, the rest the hardware division."""
+    """rt_device.h norm() as the kernels build it (core square root and
+    shared-reciprocal quotients, lanes out of range redone by norm_len_fix):
+    the quotients equal IEEE `/` for ~270M random vectors (safe range, its
+    edges, denormals, specials); most lanes take the fast path, the rest the
+    hardware division."""
     import subprocess
     exe = os.path.join(os.path.dirname(__file__), "hip", "div_check")
     if not os.path.exists(exe):
@@ -568,7 +569,7 @@ def _csg_far_scene(width, height):
     raised above the horizon, with a low light behind the camera: the shadow
     rays of ground points 100-300 units out cross the composite from
     |origin| > 100, so the composite search's far-origin shift (rt_render.h
-    csg_hit, RT_CSG_FAR) and its spatial leaf groups (>= RT_CSG_GROUP_MIN
+    csg_hit) and its spatial leaf groups (>= CSG_GROUP_MIN = 16
     leaves; the plane in an unbounded group) both run. A mirror wall 300
     units out closes the ground."""
     glass = S.material((0.9, 1.0, 0.9), 0.2, 0.0, 0.8, 1.5, 0.5, 0.8, 60.0)
@@ -674,7 +675,7 @@ def _brute(ctx, packed, y0=0, y1=None):
 @pytest.mark.parametrize("seed,n", [(5, 150), (6, 240)])
 def test_streamed_brute_force_mixed_scene_matches_oracle(ctx, spec_ctx, seed, n):
     """>= 150 mixed objects (spheres, cubes, cylinders, two planes, exact t
-    ties): far beyond RT_LDS_MAX, so object records stream through the
+    ties): far beyond LDS_MAX_BYTES, so object records stream through the
     per-wave LDS chunks; generic and specialised kernels, bytes + counters."""
     packed = rt.scene.convert(_mixed_scene(seed, n, 96, 64))
     ref, ost = oracle_bind.render_rows(packed)
