@@ -189,9 +189,16 @@ def test_first_call_renders_generic_then_switches(name, size):
     """A fresh process's first Render() of a new scene shape does not wait for
     hipRTC: it renders with the generic kernel (same bytes and counters) while
     the specialised kernel compiles in the background, and a later call
-    switches to it -- bytes and counters equal the oracle before and after."""
+    switches to it -- bytes and counters equal the oracle before and after.
+
+    The shape has to be new to the compiler as well: the code-object manager
+    keeps compiled kernels in an on-disk cache per user, which tests that ran
+    earlier fill with these very kernels. A compile served from that cache
+    can end before the first call does (most of which is HIP's start-up), and
+    nothing is pending any more when it returns; a real compile outlasts it.
+    The fresh process therefore runs with that cache off."""
     r = subprocess.run([sys.executable, "-c", FIRST_CALL, name, str(size[0]), str(size[1])],
-                       capture_output=True, text=True, timeout=300)
+                       capture_output=True, text=True, timeout=300, env=dict(os.environ, AMD_COMGR_CACHE="0"))
     assert r.returncode == 0, r.stdout + r.stderr
     calls = json.loads(r.stdout.strip().splitlines()[-1])
     assert calls[0]["specialized"] == 0 and calls[0]["pending"] >= 1, calls[0]
