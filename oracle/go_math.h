@@ -489,4 +489,11 @@ static inline uint32_t go_f64_to_u32(double v) {
     return (uint32_t)(uint64_t)(int64_t)v;
 }
 
+/* int64(v) for float64 v on amd64: CVTTSD2SQ alone (floor / frac of the GML
+ * evaluator); NaN and anything outside [-2^63, 2^63) give MinInt64. */
+static inline int64_t go_f2i(double v) {
+    if (!(v >= -9223372036854775808.0 && v < 9223372036854775808.0)) return INT64_MIN;
+    return (int64_t)v;
+}
+
 #endif /* GO_MATH_H */

@@ -934,6 +934,8 @@ double oracle_go_log_amd64(double x) { return go_log_amd64(x); }
 double oracle_go_exp(double x) { return go_exp(x); }
 double oracle_go_log(double x) { return go_log(x); }
 double oracle_go_acos(double x) { return go_acos(x); }
+double oracle_go_asin(double x) { return go_asin(x); }
+int64_t oracle_go_f2i(double v) { return go_f2i(v); }
 double oracle_go_atan2(double y, double x) { return go_atan2(y, x); }
 double oracle_go_tan(double x) { return go_tan(x); }
 double oracle_go_sin(double x) { return go_sin(x); }

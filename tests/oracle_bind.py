@@ -49,9 +49,11 @@ def lib():
             getattr(l, fn).restype = C.c_double
         l.oracle_pcg_float64.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
         l.oracle_pcg_float64.restype = None
-        for fn in ("oracle_go_acos",):
+        for fn in ("oracle_go_acos", "oracle_go_asin"):
             getattr(l, fn).argtypes = [C.c_double]
             getattr(l, fn).restype = C.c_double
+        l.oracle_go_f2i.argtypes = [C.c_double]
+        l.oracle_go_f2i.restype = C.c_int64
         l.oracle_go_atan2.argtypes = [C.c_double, C.c_double]
         l.oracle_go_atan2.restype = C.c_double
         l.oracle_set_surface_callback.argtypes = [SURFACE_CB]
