@@ -257,6 +257,34 @@ class rt_adaptive(C.Structure):
         ("tolerance", C.c_double),    # >= 0, not NaN; +inf: every pixel stops at min_samples
     ]
 
+
+class rt_aov_out(C.Structure):
+    """The feature buffers of rt_render_camera_aov_async: device pointers, any
+    may be NULL, not all."""
+    _fields_ = [
+        ("depth", C.c_void_p),     # double, 1 per pixel
+        ("normal", C.c_void_p),    # double, 3 per pixel
+        ("albedo", C.c_void_p),    # double, 3 per pixel
+        ("coverage", C.c_void_p),  # double, 1 per pixel
+        ("ids", C.c_void_p),       # int32, 4 per pixel (AOV_IDS_DTYPE), 16-byte aligned
+    ]
+
+
+AOV_NAMES = ("depth", "normal", "albedo", "coverage", "ids")
+
+
+class rt_denoise(C.Structure):
+    """The a-trous filter's parameters (rt_denoise_atrous_async). A sigma > 0
+    and finite turns its term on; 0 or +inf turns it off."""
+    _fields_ = [
+        ("iterations", C.c_int32),    # 1..8; 0: 5
+        ("reserved", C.c_int32),      # must be 0
+        ("sigma_color", C.c_double),
+        ("sigma_normal", C.c_double),
+        ("sigma_depth", C.c_double),
+        ("sigma_albedo", C.c_double),
+    ]
+
 # numpy structured dtypes of the same layout as rt_ray / rt_hit / rt_radiance
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("tmax", "<f8"), ("exclude", "<i4"),
                       ("reserved", "<i4")])
@@ -264,6 +292,8 @@ HIT_DTYPE = np.dtype([("t", "<f8"), ("point_obj", "<f8", (3,)), ("point_world", 
                       ("normal_world", "<f8", (3,)), ("object", "<i4"), ("face", "<i4"), ("kind", "<i4"),
                       ("material", "<i4")])
 RADIANCE_DTYPE = np.dtype([("color", "<f8", (3,)), ("object", "<i4"), ("rays", "<i4")])
+# one pixel of rt_aov_out.ids: sample 0's hit as rt_hit codes it (a miss: -1, 0, 0, 0)
+AOV_IDS_DTYPE = np.dtype([("object", "<i4"), ("face", "<i4"), ("kind", "<i4"), ("material", "<i4")])
 
 
 class PackedScene:

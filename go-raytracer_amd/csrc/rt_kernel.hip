@@ -2841,4 +2841,5 @@ int rt_debug_run_surface(rt_context* c, int program, int n, const long long* fac
 #include "rt_query.hip"
 #include "rt_trace.hip"
 #include "rt_camera.hip"
+#include "rt_aov.hip"
 #include "rt_render_api.hip"

@@ -16,6 +16,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "csrc", "librtamd.so")
 
 _lib = None
+# sigmas RenderContext.denoise and the CLI use when none are given (README "Denoising")
+DENOISE_DEFAULTS = {"color": 0.6, "normal": 0.5, "depth": 1.0, "albedo": 0.25}
 
 
 class RenderError(RuntimeError):
@@ -111,6 +113,10 @@ def load_library(path=None):
     l.rt_render_camera_adaptive_async.restype = i
     l.rt_render_camera_adaptive_plan.argtypes = [vp, vp, vp, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     l.rt_render_camera_adaptive_plan.restype = i
+    l.rt_render_camera_aov_async.argtypes = [vp, vp, i, i, vp, vp]
+    l.rt_render_camera_aov_async.restype = i
+    l.rt_denoise_atrous_async.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.rt_denoise_atrous_async.restype = i
     if l.rt_abi_version() != abi.RT_ABI_VERSION:
         raise RenderError("librtamd ABI version mismatch")
     _lib = l
@@ -601,6 +607,121 @@ class RenderContext:
                                                        int(h if y1 is None else y1), C.byref(chunks), C.byref(passes)),
                "rt_render_camera_adaptive_plan")
         return chunks.value, passes.value
+
+    # ---- feature buffers (include/rt_abi.h rt_aov_out, rt_render_camera_aov_async) ----
+    def render_camera_aov_async(self, cam, y0, y1, depth=None, normal=None, albedo=None, coverage=None, ids=None,
+                                stream=None):
+        """Enqueue the feature buffers of rows [y0, y1) of `cam`'s frame (None:
+        the zero camera) into any of `depth` [rows, W], `normal` [rows, W, 3],
+        `albedo` [rows, W, 3], `coverage` [rows, W] (float64 CUDA tensors) and
+        `ids` (int32 [rows, W, 4]: sample 0's object, face, kind, material).
+        One launch, nothing allocated; needs no ordering with the context's
+        other calls."""
+        torch = self.torch
+        who = "render_camera_aov_async"
+        cam, w, _, _ = self._camera_frame(cam)
+        n = max(0, int(y1) - int(y0)) * w
+        out = abi.rt_aov_out()
+        for name, t, per in (("depth", depth, 1), ("normal", normal, 3), ("albedo", albedo, 3),
+                             ("coverage", coverage, 1)):
+            if t is not None:
+                assert t.dtype == torch.float64, "%s: %s must be a float64 tensor" % (who, name)
+                setattr(out, name, self._camera_out(t, n * per * 8, who, name).value)
+        if ids is not None:
+            assert ids.dtype == torch.int32, who + ": ids must be an int32 tensor"
+            out.ids = self._camera_out(ids, n * 16, who, "ids").value
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_render_camera_aov_async(self.handle, C.byref(cam), int(y0), int(y1), C.byref(out),
+                                                   C.c_void_p(s.cuda_stream)), "rt_render_camera_aov_async")
+
+    def render_camera_aov(self, cam=None, y0=0, y1=None, which=abi.AOV_NAMES):
+        """Synchronous feature buffers of rows [y0, y1) -> a dict of numpy
+        arrays for the names in `which` (abi.AOV_NAMES): float64 depth and
+        coverage [rows, W], normal and albedo [rows, W, 3], and ids, an
+        abi.AOV_IDS_DTYPE array [rows, W]."""
+        torch = self.torch
+        cam, w, h, _ = self._camera_frame(cam)
+        if y1 is None:
+            y1 = h
+        rows = max(0, y1 - y0)
+        dev = "cuda:%d" % self.device
+        shapes = {"depth": (rows, w), "normal": (rows, w, 3), "albedo": (rows, w, 3), "coverage": (rows, w),
+                  "ids": (rows, w, 4)}
+        bufs = {}
+        for name in which:
+            if name not in shapes:
+                raise ValueError("unknown feature buffer %r (one of %s)" % (name, ", ".join(abi.AOV_NAMES)))
+            bufs[name] = torch.empty(shapes[name], dtype=torch.int32 if name == "ids" else torch.float64, device=dev)
+        self.render_camera_aov_async(cam, y0, y1, stream=None, **bufs)
+        torch.cuda.synchronize(self.device)
+        out = {k: t.cpu().numpy() for k, t in bufs.items()}
+        if "ids" in out:
+            out["ids"] = out["ids"].view(abi.AOV_IDS_DTYPE).reshape(rows, w)
+        return out
+
+    # ---- the guided a-trous denoiser (include/rt_abi.h rt_denoise, rt_denoise_atrous_async) ----
+    @staticmethod
+    def denoise_params(iterations=0, color=0.0, normal=0.0, depth=0.0, albedo=0.0):
+        """An abi.rt_denoise: `iterations` 1..8 (0: 5) and the sigma of each
+        term (0 or +inf: the term is off)."""
+        dn = abi.rt_denoise()
+        dn.iterations = int(iterations)
+        dn.sigma_color, dn.sigma_normal = float(color), float(normal)
+        dn.sigma_depth, dn.sigma_albedo = float(depth), float(albedo)
+        return dn
+
+    def denoise_async(self, params, color, out, tmp=None, normal=None, depth=None, albedo=None, rgba=None,
+                      stream=None):
+        """Enqueue the a-trous filter of the whole frame `color` (float64 CUDA
+        tensor [H, W, 3], never written) into `out` (same shape), one launch
+        per iteration. `tmp` (same shape) is needed for more than one
+        iteration; the guides `normal` [H, W, 3], `depth` [H, W] and `albedo`
+        [H, W, 3] are needed where their term is on; `rgba` (uint8 [H, W, 4])
+        optionally receives the quantised result. Needs no scene."""
+        torch = self.torch
+        who = "denoise_async"
+        assert color.dim() == 3 and color.shape[2] == 3, who + ": color must be [H, W, 3]"
+        h, w = int(color.shape[0]), int(color.shape[1])
+        ptrs = []
+        for name, t, per in (("color", color, 3), ("normal", normal, 3), ("depth", depth, 1), ("albedo", albedo, 3),
+                             ("out", out, 3), ("tmp", tmp, 3)):
+            if t is None:
+                ptrs.append(None)
+                continue
+            assert t.dtype == torch.float64, "%s: %s must be a float64 tensor" % (who, name)
+            ptrs.append(self._camera_out(t, h * w * per * 8, who, name))
+        rp = None
+        if rgba is not None:
+            assert rgba.dtype == torch.uint8, who + ": rgba must be a uint8 tensor"
+            rp = self._camera_out(rgba, h * w * 4, who, "rgba")
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        _check(self.lib.rt_denoise_atrous_async(self.handle, C.byref(params), w, h, *ptrs, rp,
+                                                C.c_void_p(s.cuda_stream)), "rt_denoise_atrous_async")
+
+    def denoise(self, mean, normal=None, depth=None, albedo=None, params=None, rgba=False):
+        """Synchronous a-trous filter of a numpy float64 [H, W, 3] mean with
+        the given guides (numpy arrays as render_camera_aov returns them) ->
+        float64 [H, W, 3]; with rgba=True -> (that, uint8 [H, W, 4]). `params`
+        None: denoise_params() with DENOISE_DEFAULTS for the guides given."""
+        torch = self.torch
+        dev = "cuda:%d" % self.device
+        if params is None:
+            d = DENOISE_DEFAULTS
+            params = self.denoise_params(0, d["color"], d["normal"] if normal is not None else 0.0,
+                                         d["depth"] if depth is not None else 0.0,
+                                         d["albedo"] if albedo is not None else 0.0)
+
+        def up(a):
+            return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+        color = up(mean)
+        out = torch.empty_like(color)
+        k = int(params.iterations) or 5
+        tmp = torch.empty_like(color) if k > 1 else None
+        img = torch.empty(tuple(color.shape[:2]) + (4,), dtype=torch.uint8, device=dev) if rgba else None
+        self.denoise_async(params, color, out, tmp, up(normal), up(depth), up(albedo), img)
+        torch.cuda.synchronize(self.device)
+        return (out.cpu().numpy(), img.cpu().numpy()) if rgba else out.cpu().numpy()
 
     def image_from_radiance(self, out, samples):
         """Average `samples` consecutive radiance records per pixel and quantise

@@ -733,6 +733,94 @@ int rt_render_camera_adaptive_async(rt_context *ctx, const rt_camera *cam, const
 int rt_render_camera_adaptive_plan(rt_context *ctx, const rt_camera *cam, const rt_adaptive *ad, int y0, int y1,
                                    int *chunks, int *passes);
 
+/* ---- Feature buffers: per-pixel depth, normal, albedo, coverage and ids of a
+ * camera render, and an edge-avoiding a-trous filter guided by them ----
+ * (csrc/rt_aov.hip). Everything is FP64, one rounding per operation, no
+ * contraction, in the order written here.
+ *
+ * Rows [y0, y1) of the camera's frame are written in [row][x] order, row y0
+ * first. S = cam->samples (0: 4). Sample s of pixel (x, y) is exactly sample s
+ * of rt_render_camera_async with the same camera -- same draws, same ray. For
+ * each sample, closestHit runs as rt_query_closest_async defines it, with
+ * tmax = +inf and exclude = -1. A sample that hits yields
+ *   t   the hit's t;
+ *   n^  nw / sqrt(nw.x * nw.x + nw.y * nw.y + nw.z * nw.z), component by
+ *       component with IEEE division, nw being rt_hit.normal_world (the
+ *       composite's flip included);
+ *   a   the surface's material colour: materials[material].color for
+ *       material >= 0; for a closure surface the colour of its program run on
+ *       the (face, u, v) the radiance kernel forms, a failing evaluation giving
+ *       (0, 0, 0) (the all-zero material). The colour is not clamped.
+ * Accumulators zt, N, A (0.0) and the integer hit count h (0): the hitting
+ * samples are added in sample order (zt = zt + t, N = N + n^, A = A + a per
+ * component, h = h + 1); misses add nothing. With inv = 1.0 / (double)S:
+ *   coverage = (double)h * inv,  normal = N * inv,  albedo = A * inv,
+ *   depth = h > 0 ? zt / (double)h : +inf
+ * so normal and albedo carry the coverage. ids is sample 0's object, face,
+ * kind, material as rt_hit codes them; a miss gives -1, 0, 0, 0. */
+typedef struct rt_aov_out {      /* device pointers; any may be NULL, not all */
+    double  *depth;              /* 1 per pixel, 8-byte aligned */
+    double  *normal;             /* 3 per pixel */
+    double  *albedo;             /* 3 per pixel */
+    double  *coverage;           /* 1 per pixel */
+    int32_t *ids;                /* 4 per pixel, 16-byte aligned: object, face, kind, material */
+} rt_aov_out;
+
+/* One launch, one lane per pixel of the band, ordered on `stream`.
+ * cam->depth and cam->chunk_pixels are validated as for camera renders and
+ * otherwise unused. RT_E_INVALID (with an rt_last_error text) for everything
+ * rt_render_camera_async rejects, and: NULL out, all five pointers NULL, a
+ * misaligned pointer. Nothing is launched then and the context stays usable.
+ * The call touches no counters, tile order, specialisation state or workspace
+ * and allocates nothing: there is no sample buffer and there are no chunks, so
+ * it needs no ordering with the other calls on the context. The answer does
+ * not depend on rt_set_accel. */
+int rt_render_camera_aov_async(rt_context *ctx, const rt_camera *cam, int y0, int y1,
+                               const rt_aov_out *out, void *stream);
+
+/* Edge-avoiding a-trous filter on a float64 mean. All buffers are whole frames
+ * of width x height pixels in [row][x] order, laid out as
+ * rt_render_camera_async (d_mean -> d_color) and rt_render_camera_aov_async
+ * (normal, depth, albedo) write them; d_out and d_tmp hold 3 doubles per pixel.
+ * Taps h = (1/16, 1/4, 3/8, 1/4, 1/16), so h[j] * h[i] is exact. K = iterations
+ * (0: 5). For iteration i = 0 .. K-1: step = 1 << i; the input is I_i, with
+ * I_0 = d_color; the output goes to d_out when K - 1 - i is even, else to
+ * d_tmp, so I_K lands in d_out. Constants, formed once on the host:
+ * ic_i = 1.0 / (s * s) with s = sigma_color * 0.5^i; in, iz, ia =
+ * 1.0 / (sigma * sigma) of the normal, depth and albedo terms.
+ *   kern(x) = x < 1.0 ? (1.0 - x) * (1.0 - x) : 0.0       (0 for NaN)
+ *   dist2(a, b) = (d0 * d0 + d1 * d1) + d2 * d2, d the componentwise a - b
+ * Pixel p = (x, y): sum = 0, wsum = 0; for dy = -2..2 (outer), dx = -2..2
+ * (inner): q = (x + dx * step, y + dy * step), skipped when outside the frame;
+ * w = h[dy + 2] * h[dx + 2]; then for each term that is on, in this order,
+ *   colour  w = w * kern(dist2(I_i[p], I_i[q]) * ic_i)
+ *   normal  w = w * kern(dist2(n[p], n[q]) * in)
+ *   depth   w = w * kern((z[p] == z[q] ? 0.0 : (z[p] - z[q]) * (z[p] - z[q])) * iz)
+ *           (two background pixels, both +inf, agree)
+ *   albedo  w = w * kern(dist2(a[p], a[q]) * ia)
+ * and the tap contributes only if w > 0.0: sum.c = sum.c + w * I_i[q].c per
+ * channel, then wsum = wsum + w. The result is sum.c / wsum (IEEE division)
+ * when wsum > 0.0, else I_i[p] unchanged. d_rgba (optional, 4-byte aligned)
+ * receives I_K quantised as the camera renders quantise their mean. */
+typedef struct rt_denoise {
+    int32_t iterations;          /* 1..8; 0: 5 */
+    int32_t reserved;            /* must be 0 */
+    double  sigma_color, sigma_normal, sigma_depth, sigma_albedo;
+                                 /* > 0 and finite: the term is on; 0 or +inf: off; negative or NaN: invalid */
+} rt_denoise;
+
+/* One launch per iteration on `stream` (a thread per pixel); the host does not
+ * wait. No scene is needed, nothing is allocated and d_color is never written.
+ * RT_E_INVALID (with an rt_last_error text): NULL context or dn, reserved != 0,
+ * iterations outside [0, 8], a negative or NaN sigma, width or height < 1 (or
+ * more than 2^31 - 1 pixels), NULL d_color or d_out, NULL d_tmp with more than
+ * one iteration, a NULL guide whose term is on, a float64 buffer not 8-byte
+ * aligned, overlapping byte ranges of d_color, d_out and d_tmp. Nothing is
+ * launched then. */
+int rt_denoise_atrous_async(rt_context *ctx, const rt_denoise *dn, int width, int height,
+                            const double *d_color, const double *d_normal, const double *d_depth,
+                            const double *d_albedo, double *d_out, double *d_tmp, void *d_rgba, void *stream);
+
 /* SSIM of two RGBA8 frames in device memory (width x height, stride 4W), the
  * reference's parity metric prim.SSIM (internal/prim/ssim.go:27-182; used by
  * raytracer_test.go:42 with threshold 0.99). Synchronous on `stream`.

@@ -39,8 +39,23 @@ fixed 64-sample frame; also the time of the same call at an infinite
 tolerance (every pass after the first is empty: what the launches alone cost)
 and of the fixed render at min_samples.
 
-usage: python scripts/query_rate.py [--configs c3,c4csg,c5] [--modes closest,occluded,radiance,camera,adaptive]
-                                    [--out FILE]
+Aov mode (not in the default modes; writes profiles/aov/aov_rate.jsonl unless
+--out says otherwise): the zero camera's five feature buffers at 1920x1080 x 4
+and x 64 samples through rt_render_camera_aov_async beside the materialised
+route -- camera_rays_ex_async + query_closest_async + a reduction in torch in
+sample order -- median of 5 timed repeats each after a warm-up; the margin of
+the comparison is the spread of the route's own repeats. Each line also says
+whether the route's buffers equal the fused call's.
+
+Denoise mode (same file): rt_denoise_atrous_async, 5 iterations, all terms on
+with the default sigmas, on a 4-sample thin-lens frame of the scene and its
+feature buffers at 1920x1080 and 3840x2160: ms per iteration beside the memory
+floor (104 B per pixel at 8 TB/s) and the FP64 floor (1.1 k operations per
+pixel at 78.6 TFLOP/s); at 1080p also the mean squared error of the raw and of
+the denoised mean against a 256-sample mean for a few sigma sets.
+
+usage: python scripts/query_rate.py [--configs c3,c4csg,c5]
+                                    [--modes closest,occluded,radiance,camera,adaptive,aov,denoise] [--out FILE]
 """
 import argparse
 import json
@@ -208,6 +223,149 @@ def adaptive_lines(torch, abi, ctx, name, seed):
     return lines
 
 
+AOV_SAMPLES, AOV_REPEATS = (4, 64), 5
+
+
+def repeats(torch, launch, warmup, n):
+    """Device-event time of each of n launches after `warmup` warm-ups."""
+    for _ in range(warmup):
+        launch()
+    out = []
+    for _ in range(n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def aov_lines(torch, abi, ctx, name, seed):
+    """rt_render_camera_aov_async (all five buffers) of the zero camera at 4
+    and 64 samples beside the materialised route it replaces: the camera's
+    rays written out, the closest-hit query, the buffers reduced in torch in
+    sample order. Median of 5 timed repeats each after one warm-up; the margin
+    of the comparison is the spread of the route's own repeats."""
+    dev = "cuda:0"
+    mats = torch.tensor([list(ctx.packed.scene.materials[i].color[:]) for i in range(int(ctx.packed.scene.num_materials))],
+                        dtype=torch.float64, device=dev).reshape(-1, 3)
+    lines = []
+    for S in AOV_SAMPLES:
+        cam = ctx.camera(samples=S)
+        n = W * H * S
+        bufs = {"depth": torch.empty((H, W), dtype=torch.float64, device=dev),
+                "normal": torch.empty((H, W, 3), dtype=torch.float64, device=dev),
+                "albedo": torch.empty((H, W, 3), dtype=torch.float64, device=dev),
+                "coverage": torch.empty((H, W), dtype=torch.float64, device=dev),
+                "ids": torch.empty((H, W, 4), dtype=torch.int32, device=dev)}
+        fused = repeats(torch, lambda: ctx.render_camera_aov_async(cam, 0, H, **bufs), 1, AOV_REPEATS)
+        rays = torch.empty(n * abi.RAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        hits = torch.empty(n * abi.HIT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        res = {}
+
+        def route():
+            ctx.camera_rays_ex_async(cam, 0, H, rays)
+            ctx.query_closest_async(rays, hits)
+            f = hits.view(torch.float64).view(H * W, S, 12)
+            i = hits.view(torch.int32).view(H * W, S, 24)
+            zt = torch.zeros(H * W, dtype=torch.float64, device=dev)
+            N = torch.zeros((H * W, 3), dtype=torch.float64, device=dev)
+            A = torch.zeros((H * W, 3), dtype=torch.float64, device=dev)
+            h = torch.zeros(H * W, dtype=torch.int32, device=dev)
+            for s in range(S):
+                hit = i[:, s, 20] >= 0
+                nw = f[:, s, 7:10]
+                ln = torch.sqrt((nw[:, 0] * nw[:, 0] + nw[:, 1] * nw[:, 1]) + nw[:, 2] * nw[:, 2])
+                m = hit.unsqueeze(1)
+                zt = zt + torch.where(hit, f[:, s, 0], 0.0)
+                N = N + torch.where(m, nw / ln.unsqueeze(1), 0.0)
+                A = A + torch.where(m, mats[i[:, s, 23].clamp(min=0).long()], 0.0)
+                h = h + hit.to(torch.int32)
+            inv = 1.0 / S
+            hd = h.to(torch.float64)
+            res["coverage"] = hd * inv
+            res["normal"] = N * inv
+            res["albedo"] = A * inv
+            res["depth"] = torch.where(h > 0, zt / hd, math.inf)
+            res["ids"] = i[:, 0, 20:24].clone()
+
+        route_ms = repeats(torch, route, 1, AOV_REPEATS)
+        closures = bool((hits.view(torch.int32).view(-1, 24)[:, 23] < 0).any().item())
+        same = {k: bool(torch.equal(res[k].reshape(bufs[k].shape), bufs[k])) for k in bufs}
+        hit_frac = float(bufs["coverage"].mean().item())
+        del rays, hits, res
+        fm, rm = float(np.median(fused)), float(np.median(route_ms))
+        spread = max(route_ms) - min(route_ms)
+        lines.append({"metric": "aov_rate", "config": name, "mode": "aov", "width": W, "height": H, "samples": S,
+                      "objects": int(ctx.packed.scene.num_objects), "bvh": bool(ctx.scene_info() & abi.RT_INFO_BVH),
+                      "fused_ms": [round(v, 4) for v in fused], "route_ms": [round(v, 4) for v in route_ms],
+                      "fused_median_ms": round(fm, 4), "route_median_ms": round(rm, 4),
+                      "route_spread_ms": round(spread, 4), "fused_over_route": round(fm / rm, 4),
+                      "fused_wins_beyond_spread": bool(fm < rm - spread),
+                      "value": round(n / fm / 1e3, 2), "unit": "Mrays/s", "mean_coverage": round(hit_frac, 4),
+                      "route_equals_fused": same, "closure_samples": closures,
+                      "route_bytes_per_ray": abi.RAY_DTYPE.itemsize * 2 + abi.HIT_DTYPE.itemsize * 2,
+                      "repeats": AOV_REPEATS, "warmup": 1, "seed": seed})
+    return lines
+
+
+DN_SIZES = ((1920, 1080), (3840, 2160))
+DN_HBM_BYTES_PER_S, DN_FP64_FLOPS = 8.0e12, 78.6e12  # the spec peaks DESIGN.md's roofline uses
+DN_BYTES_PER_PIXEL, DN_FLOP_PER_PIXEL = 104, 1100
+DN_CANDIDATES = ((0.6, 0.5, 1.0, 0.25), (0.3, 0.5, 1.0, 0.25), (1.2, 0.5, 1.0, 0.25), (0.0, 0.5, 1.0, 0.25),
+                 (0.6, 0.25, 0.5, 0.1), (0.6, 1.0, 2.0, 0.5), (0.6, 0.0, 0.0, 0.0))
+
+
+def denoise_lines(torch, abi, ctx, name, seed, default_sigmas):
+    """rt_denoise_atrous_async, K = 5, all terms on, on a 4-sample thin-lens
+    frame of the scene with its feature buffers, at 1080p and 4K: ms per
+    iteration (median of 5 repeats of the 5-iteration call) beside the memory
+    and FP64 floors; at 1080p also the mean squared error of the raw and of
+    the denoised mean against a 256-sample mean, for each candidate sigma set."""
+    dev = "cuda:0"
+    lines = []
+    for (w, h) in DN_SIZES:
+        kw = dict(model="thinlens", size=(w, h), aperture=0.2, focus=4.5)
+        cam = ctx.camera(samples=4, **kw)
+        mean = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+        ctx.render_camera_async(cam, 0, h, mean=mean)
+        g = {"normal": torch.empty((h, w, 3), dtype=torch.float64, device=dev),
+             "depth": torch.empty((h, w), dtype=torch.float64, device=dev),
+             "albedo": torch.empty((h, w, 3), dtype=torch.float64, device=dev)}
+        ctx.render_camera_aov_async(cam, 0, h, **g)
+        out, tmp = torch.empty_like(mean), torch.empty_like(mean)
+        dn = ctx.denoise_params(5, *default_sigmas)
+        ms = repeats(torch, lambda: ctx.denoise_async(dn, mean, out, tmp, **g), 1, AOV_REPEATS)
+        one = []
+        for i in range(5):  # the first i + 1 iterations (a later iteration cannot be launched alone)
+            dk = ctx.denoise_params(i + 1, *default_sigmas)
+            one.append(round(float(np.median(repeats(torch, lambda: ctx.denoise_async(dk, mean, out, tmp, **g), 1, 3))), 4))
+        px = w * h
+        line = {"metric": "denoise_rate", "config": name, "mode": "denoise", "width": w, "height": h, "iterations": 5,
+                "sigmas": list(default_sigmas), "variant": "LDS tile with halo for steps 1 and 2, global loads beyond; thread per pixel",
+                "ms": [round(v, 4) for v in ms], "ms_per_iteration": round(float(np.median(ms)) / 5, 4),
+                "first_k_iterations_ms": one,
+                "floor_memory_ms": round(px * DN_BYTES_PER_PIXEL / DN_HBM_BYTES_PER_S * 1e3, 4),
+                "floor_fp64_ms": round(px * DN_FLOP_PER_PIXEL / DN_FP64_FLOPS * 1e3, 4),
+                "repeats": AOV_REPEATS, "warmup": 1, "seed": seed}
+        if (w, h) == DN_SIZES[0]:
+            ref = torch.empty_like(mean)
+            ctx.render_camera_async(ctx.camera(samples=256, **kw), 0, h, mean=ref)
+            torch.cuda.synchronize()
+            line["mse_raw_vs_256"] = float(((mean - ref) ** 2).mean().item())
+            q = []
+            for sg in DN_CANDIDATES:
+                ctx.denoise_async(ctx.denoise_params(5, *sg), mean, out, tmp, **g)
+                torch.cuda.synchronize()
+                q.append({"sigmas": list(sg), "mse_vs_256": float(((out - ref) ** 2).mean().item())})
+            line["quality"] = q
+            del ref
+        lines.append(line)
+        del mean, out, tmp, g
+    return lines
+
+
 def camera_rays(fov_deg, seed):
     g = np.random.default_rng(seed)
     vw = 2.0 * math.tan(math.radians(fov_deg) / 2.0)
@@ -270,7 +428,21 @@ def main():
             for ln in adaptive_lines(torch, abi, ctx, name, args.seed):
                 lines.append(ln)
                 print(json.dumps(ln), flush=True)
+        if "aov" in modes:
+            for ln in aov_lines(torch, abi, ctx, name, args.seed):
+                lines.append(ln)
+                print(json.dumps(ln), flush=True)
+        if "denoise" in modes:
+            d = pkg.render.DENOISE_DEFAULTS
+            for ln in denoise_lines(torch, abi, ctx, name, args.seed, (d["color"], d["normal"], d["depth"], d["albedo"])):
+                lines.append(ln)
+                print(json.dumps(ln), flush=True)
     ctx.close()
+    if args.out is None and ("aov" in args.modes.split(",") or "denoise" in args.modes.split(",")):
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "aov",
+                                "aov_rate.jsonl")
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        lines = [ln for ln in lines if ln["mode"] in ("aov", "denoise")]
     if args.out is None and "adaptive" in args.modes.split(","):
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "adaptive",
                                 "adaptive_rate.jsonl")
