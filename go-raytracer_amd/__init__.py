@@ -3,8 +3,8 @@
 Layout:
   csrc/rt_kernel.hip   HIP megakernel (gfx950) + the C ABI of include/rt_abi.h
   csrc/rt_ssim.hip     device SSIM (the reference's parity metric)
-  csrc/rt_camera.hip   camera renders: ray source in the radiance kernel, resolve; adaptive passes
-  csrc/rt_aov.hip      feature buffers of a camera render; the guided a-trous denoiser
+  csrc/rt_camera.hip   camera renders: ray source in the radiance kernel, resolve; adaptive passes; per-pixel variance
+  csrc/rt_aov.hip      feature buffers of a camera render; the guided a-trous denoiser and its variance-guided mode
   abi.py               ctypes mirror of include/rt_abi.h
   scene.py             host scene values, BFS flattening, surface baking
   gomath.py            Go float64 host math (transform matrices)

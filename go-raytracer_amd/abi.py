@@ -285,6 +285,10 @@ class rt_denoise(C.Structure):
         ("sigma_albedo", C.c_double),
     ]
 
+
+# the variance-guided filter (rt_denoise_atrous_var_async): added to kc2 * g under the reciprocal
+RT_DENOISE_VAR_EPS = 1e-10
+
 # numpy structured dtypes of the same layout as rt_ray / rt_hit / rt_radiance
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,)), ("tmax", "<f8"), ("exclude", "<i4"),
                       ("reserved", "<i4")])

@@ -23,6 +23,10 @@ also writes the camera's feature buffers (RenderContext.render_camera_aov) as
 filter (RenderContext.denoise; guides: normal, depth, albedo) and writes
 <image stem>.denoised<ext>; --denoise-iterations K and --denoise-sigmas C,N,Z,A
 (colour, normal, depth, albedo; 0 turns a term off) replace the defaults.
+--denoise-variance (with --denoise) renders the per-pixel variance of the mean
+too and runs the variance-guided filter: C is then in standard deviations
+(default render.DENOISE_VAR_COLOR). --variance-map FILE writes that variance
+as an .npy of float64 [H, W, 3].
 Either flag alone selects the camera render of the scene's own camera.
 (from the repo root the package directory is go-raytracer_amd/; see
 __graft_entry__.load_package)
@@ -77,14 +81,18 @@ def aov_from_args(a):
 
 
 def denoise_from_args(a):
-    """The abi.rt_denoise of --denoise / --denoise-iterations / --denoise-sigmas, or None without --denoise."""
+    """The abi.rt_denoise of --denoise / --denoise-iterations / --denoise-sigmas, or None without --denoise.
+    With --denoise-variance the default colour sigma is render.DENOISE_VAR_COLOR standard deviations."""
     if not getattr(a, "denoise", False):
         if getattr(a, "denoise_iterations", None) is not None or getattr(a, "denoise_sigmas", None) is not None:
             raise SystemExit("--denoise-iterations and --denoise-sigmas need --denoise")
+        if getattr(a, "denoise_variance", False):
+            raise SystemExit("--denoise-variance needs --denoise")
         return None
-    from .render import DENOISE_DEFAULTS, RenderContext
+    from .render import DENOISE_DEFAULTS, DENOISE_VAR_COLOR, RenderContext
     d = DENOISE_DEFAULTS
-    sig = [d["color"], d["normal"], d["depth"], d["albedo"]]
+    sig = [DENOISE_VAR_COLOR if getattr(a, "denoise_variance", False) else d["color"], d["normal"], d["depth"],
+           d["albedo"]]
     if a.denoise_sigmas is not None:
         try:
             sig = [float(v) for v in a.denoise_sigmas.split(",")]
@@ -119,7 +127,7 @@ def aov_view(name, buf):
 
 
 def render_program(path, out_dir=None, device=0, stats=False, log=sys.stdout, extensions=False, camera=None,
-                   adaptive=None, samples_map=None, aov=None, denoise=None):
+                   adaptive=None, samples_map=None, aov=None, denoise=None, denoise_variance=False, variance_map=None):
     from . import gml, imageio, scene
     from .render import RenderContext
     ctx = RenderContext(device)
@@ -131,16 +139,25 @@ def render_program(path, out_dir=None, device=0, stats=False, log=sys.stdout, ex
         ctx.set_scene(packed)
         ctx.read_stats(reset=True)
         cam = camera
-        if cam is None and (adaptive is not None or aov or denoise is not None):
+        want_var = bool(denoise_variance or variance_map)
+        if cam is None and (adaptive is not None or aov or denoise is not None or want_var):
             cam = RenderContext.camera()
         mean = None  # the float64 mean: wanted by --denoise only
+        var = None   # the variance of that mean: wanted by --denoise-variance and --variance-map
         if adaptive is not None:
-            got = ctx.render_camera_adaptive(cam, adaptive, mean=denoise is not None, samples=True)
-            img, counts = got[0], got[-1]
+            got = ctx.render_camera_adaptive(cam, adaptive, mean=denoise is not None, samples=True, var=want_var)
+            img, counts = got[0], got[-2 if want_var else -1]
             if denoise is not None:
                 mean = got[1]
+            if want_var:
+                var = got[-1]
             if samples_map:
                 imageio.write_image(samples_map, samples_image(counts, int(cam.samples) or 4))
+        elif want_var:
+            got = ctx.render_camera(cam, mean=denoise is not None, var=True)
+            img, var = got[0], got[-1]
+            if denoise is not None:
+                mean = got[1]
         elif cam is not None and denoise is not None:
             img, mean = ctx.render_camera(cam, mean=True)
         else:
@@ -150,6 +167,11 @@ def render_program(path, out_dir=None, device=0, stats=False, log=sys.stdout, ex
         dst = os.path.join(out_dir, name) if out_dir else name
         imageio.write_image(dst, img)
         written.append(dst)
+        if variance_map:
+            import numpy as np
+            with open(variance_map, "wb") as f:  # (the name as given: numpy.save would append .npy to a path)
+                np.save(f, var)
+            written.append(variance_map)
         if aov or denoise is not None:
             import numpy as np
             need = set(aov or ())
@@ -164,7 +186,8 @@ def render_program(path, out_dir=None, device=0, stats=False, log=sys.stdout, ex
                     imageio.write_image(dst + "." + n + ".png", aov_view(n, bufs[n]))
                     written.append(dst + "." + n + ".png")
             if denoise is not None:
-                _, dimg = ctx.denoise(mean, bufs.get("normal"), bufs.get("depth"), bufs.get("albedo"), denoise, rgba=True)
+                _, dimg = ctx.denoise(mean, bufs.get("normal"), bufs.get("depth"), bufs.get("albedo"), denoise,
+                                      rgba=True, var=var if denoise_variance else None)
                 stem, ext = os.path.splitext(dst)
                 imageio.write_image(stem + ".denoised" + ext, dimg)
                 written.append(stem + ".denoised" + ext)
@@ -208,6 +231,10 @@ def build_parser():
     ap.add_argument("--denoise-iterations", type=int, default=None, metavar="K", help="iterations of the filter (1..8)")
     ap.add_argument("--denoise-sigmas", default=None, metavar="C,N,Z,A",
                     help="sigmas of the colour, normal, depth and albedo terms (0: off)")
+    ap.add_argument("--denoise-variance", action="store_true",
+                    help="with --denoise: the variance-guided filter; C of --denoise-sigmas is in standard deviations")
+    ap.add_argument("--variance-map", default=None, metavar="FILE",
+                    help="write the variance of the camera render's mean as an .npy of float64 [H, W, 3]")
     return ap
 
 
@@ -221,7 +248,8 @@ def main(argv=None):
         os.makedirs(a.out_dir, exist_ok=True)
     for f in a.files:
         for w in render_program(f, a.out_dir, a.device, a.stats, extensions=a.extensions, camera=cam,
-                                adaptive=ad, samples_map=a.samples_map, aov=aov, denoise=dn):
+                                adaptive=ad, samples_map=a.samples_map, aov=aov, denoise=dn,
+                                denoise_variance=a.denoise_variance, variance_map=a.variance_map):
             print("wrote", w)
     return 0
 

@@ -1,6 +1,8 @@
 // rt_camera.hip -- camera renders (include/rt_abi.h rt_camera,
 // rt_camera_rays_async, rt_render_camera_async, rt_render_camera_chunks,
-// rt_render_camera_adaptive_async, rt_render_camera_adaptive_plan).
+// rt_render_camera_adaptive_async, rt_render_camera_adaptive_plan, and the
+// two renders with a variance output, rt_render_camera_var_async and
+// rt_render_camera_adaptive_var_async).
 //
 // The radiance kernel of rt_trace.hip with a ray source of its own, plus a
 // resolve step. rt_trace_kernel<.., GEN = true> hands out tickets exactly as a
@@ -38,6 +40,13 @@
 // this refill out of the fixed render's instantiations, whose registers have
 // no room for it (DESIGN.md "Adaptive camera renders"). An empty pass drains
 // at the first refill; nothing can hang, by the argument above.
+//
+// Variance (rt_render_camera_var_async, rt_render_camera_adaptive_var_async):
+// the squared standard error of each pixel's mean from the sums the adaptive
+// rule already keeps (cam_var). The fixed render resolves through
+// cam_resolve_var_kernel, a sibling of cam_resolve_kernel that also carries
+// the sum of squares, only when the caller gives a d_var; the adapt kernel
+// writes it where it writes the mean. Nothing else of a render changes.
 //
 // PCG position: sample s of row y starts ((y mod 20) * S + s) * D draws into
 // its column's strip stream (D draws per sample), at most 81 916 < 2^17. The
@@ -227,6 +236,48 @@ __global__ __launch_bounds__(WG) void cam_resolve_kernel(const rt_radiance* __re
   if (rgba) rgba[q] = pack_rgba8(c);
 }
 
+// A channel's squared standard error of the mean from its sum, sum of squares
+// and mean (include/rt_abi.h "Variance of a camera render"): the adaptive
+// rule's e_c, a negative estimate clamped to 0, a NaN kept.
+__device__ __forceinline__ double cam_var(double sum, double sq, double m, double den) {
+  const double e = (sq - sum * m) / den;
+  return e < 0.0 ? 0.0 : e;
+}
+
+// cam_resolve_kernel with the second moment (rt_render_camera_var_async with a
+// d_var): Sum as there, Q beside it in the adaptive state's order, and the
+// variance of the mean written next to the mean. A sibling, not a template
+// parameter, so the kernel above stays the code object it was.
+__global__ __launch_bounds__(WG) void cam_resolve_var_kernel(const rt_radiance* __restrict__ rec, int npix, int S,
+                                                              double inv, long long px0, uint32_t* rgba, double* mean,
+                                                              double* var) {
+  const int p = (int)(blockIdx.x * WG + threadIdx.x);
+  if (p >= npix) return;
+  const Q16* rp = reinterpret_cast<const Q16*>(rec + (size_t)p * S);
+  Q16 a = rp[0], b = rp[1];
+  d3 sum = mk(a.a, a.b, b.a);
+  d3 sq = mul(sum, sum);
+  for (int s = 1; s < S; s++) {
+    a = rp[2 * s];
+    b = rp[2 * s + 1];
+    const d3 c = mk(a.a, a.b, b.a);
+    sum = add(sum, c);
+    sq = add(sq, mul(c, c));
+  }
+  const d3 c = scale(sum, inv);
+  const double den = (double)(S * (S - 1));
+  const long long q = px0 + p;
+  if (mean) {
+    mean[q * 3 + 0] = c.x;
+    mean[q * 3 + 1] = c.y;
+    mean[q * 3 + 2] = c.z;
+  }
+  var[q * 3 + 0] = cam_var(sum.x, sq.x, c.x, den);
+  var[q * 3 + 1] = cam_var(sum.y, sq.y, c.y, den);
+  var[q * 3 + 2] = cam_var(sum.z, sq.z, c.z, den);
+  if (rgba) rgba[q] = pack_rgba8(c);
+}
+
 // One pass of an adaptive render (include/rt_abi.h "Adaptive camera renders").
 struct AdaptArgs {
   const rt_radiance* rec;      // the pass's records: entry j's b samples at rec[j * b ..]
@@ -242,6 +293,7 @@ struct AdaptArgs {
   uint32_t* rgba;
   double* mean;
   int32_t* samples;
+  double* var;                 // the variance of the final pixels' means (NULL: not wanted)
 };
 
 // One thread per active list entry: the entry's b records added to the pixel's
@@ -295,6 +347,11 @@ __global__ __launch_bounds__(WG) void cam_adapt_kernel(AdaptArgs A) {
         A.mean[q * 3 + 0] = m.x;
         A.mean[q * 3 + 1] = m.y;
         A.mean[q * 3 + 2] = m.z;
+      }
+      if (A.var) {
+        A.var[q * 3 + 0] = cam_var(sum.x, sq.x, m.x, den);
+        A.var[q * 3 + 1] = cam_var(sum.y, sq.y, m.y, den);
+        A.var[q * 3 + 2] = cam_var(sum.z, sq.z, m.z, den);
       }
       if (A.rgba) A.rgba[q] = pack_rgba8(m);
       if (A.samples) A.samples[q] = A.n;
@@ -431,6 +488,14 @@ int cam_out_check(const void* d_rgba, const double* d_mean, const char* who) {
   return RT_OK;
 }
 
+// d_var of the two renders that write a variance: NULL is "not wanted"
+int cam_var_check(const double* d_var, int S, const char* who) {
+  if (!d_var) return RT_OK;
+  if (((uintptr_t)d_var & 7) != 0) return fail(RT_E_INVALID, std::string(who) + ": d_var must be 8-byte aligned");
+  if (S < 2) return fail(RT_E_INVALID, std::string(who) + ": d_var needs at least 2 samples");
+  return RT_OK;
+}
+
 // Adaptive renders: the pass schedule and the chunking that goes with it.
 constexpr int CAM_ADAPT_MAX_PASSES = 12;     // min_samples 2 -> cap 1024: 10 passes
 constexpr int CAM_ADAPT_MAX_CHUNK = 524288;  // pixels of a chunk, at most: bounds the state and the lists (28 MiB)
@@ -495,13 +560,20 @@ int rt_render_camera_chunks(rt_context* c, const rt_camera* cam, int y0, int y1)
   return P.chunks;
 }
 
-int rt_render_camera_async(rt_context* c, const rt_camera* cam, int y0, int y1, void* d_rgba, double* d_mean,
-                           void* stream) {
-  const char* who = "rt_render_camera_async";
+}  // extern "C"
+
+namespace {
+
+// rt_render_camera_async (`var_call` false: d_var is NULL) and rt_render_camera_var_async
+int cam_render(rt_context* c, const rt_camera* cam, int y0, int y1, void* d_rgba, double* d_mean, double* d_var,
+               void* stream, const char* who, bool var_call) {
   CamPlan P;
   if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
-  if (!d_rgba && !d_mean) return fail(RT_E_INVALID, std::string(who) + ": d_rgba and d_mean are both NULL");
+  if (!d_rgba && !d_mean && !d_var)
+    return fail(RT_E_INVALID, std::string(who) + (var_call ? ": d_rgba, d_mean and d_var are all NULL"
+                                                           : ": d_rgba and d_mean are both NULL"));
   if (int rc = cam_out_check(d_rgba, d_mean, who); rc != RT_OK) return rc;
+  if (int rc = cam_var_check(d_var, P.A.S, who); rc != RT_OK) return rc;
   const DevScene& s = c->sc;
   DeviceGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -524,12 +596,27 @@ int rt_render_camera_async(rt_context* c, const rt_camera* cam, int y0, int y1, 
     Q.cam.first = P.A.first + (int)px0;
     void* targs[] = {(void*)&blob, (void*)&Q};
     HIP_TRY(hipLaunchKernel(kfn, dim3((unsigned)wgs), dim3(WG), targs, 0, st));
-    void* rargs[] = {(void*)&rec, (void*)&npix, (void*)&S, (void*)&inv, (void*)&px0, (void*)&rgba, (void*)&d_mean};
-    HIP_TRY(hipLaunchKernel((const void*)cam_resolve_kernel, dim3((unsigned)((npix + WG - 1) / WG)), dim3(WG), rargs, 0,
-                            st));
+    void* rargs[] = {(void*)&rec,  (void*)&npix,   (void*)&S,    (void*)&inv, (void*)&px0,
+                     (void*)&rgba, (void*)&d_mean, (void*)&d_var};  // (the plain kernel takes the first seven)
+    HIP_TRY(hipLaunchKernel(d_var ? (const void*)cam_resolve_var_kernel : (const void*)cam_resolve_kernel,
+                            dim3((unsigned)((npix + WG - 1) / WG)), dim3(WG), rargs, 0, st));
   }
   HIP_TRY(hipGetLastError());
   return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_camera_async(rt_context* c, const rt_camera* cam, int y0, int y1, void* d_rgba, double* d_mean,
+                           void* stream) {
+  return cam_render(c, cam, y0, y1, d_rgba, d_mean, nullptr, stream, "rt_render_camera_async", false);
+}
+
+int rt_render_camera_var_async(rt_context* c, const rt_camera* cam, int y0, int y1, void* d_rgba, double* d_mean,
+                               double* d_var, void* stream) {
+  return cam_render(c, cam, y0, y1, d_rgba, d_mean, d_var, stream, "rt_render_camera_var_async", true);
 }
 
 int rt_render_camera_adaptive_plan(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1,
@@ -544,18 +631,25 @@ int rt_render_camera_adaptive_plan(rt_context* c, const rt_camera* cam, const rt
   return RT_OK;
 }
 
-int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1,
-                                    void* d_rgba, double* d_mean, int32_t* d_samples, void* stream) {
-  const char* who = "rt_render_camera_adaptive_async";
+}  // extern "C"
+
+namespace {
+
+// rt_render_camera_adaptive_async (`var_call` false: d_var is NULL) and rt_render_camera_adaptive_var_async
+int cam_render_adaptive(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1, void* d_rgba,
+                        double* d_mean, int32_t* d_samples, double* d_var, void* stream, const char* who,
+                        bool var_call) {
   CamPlan P;
   AdaptPlan D;
   if (int rc = cam_setup(c, cam, y0, y1, who, P); rc != RT_OK) return rc;
   if (int rc = adapt_setup(ad, cam, who, P, D); rc != RT_OK) return rc;
-  if (!d_rgba && !d_mean && !d_samples)
-    return fail(RT_E_INVALID, std::string(who) + ": d_rgba, d_mean and d_samples are all NULL");
+  if (!d_rgba && !d_mean && !d_samples && !d_var)
+    return fail(RT_E_INVALID, std::string(who) + (var_call ? ": d_rgba, d_mean, d_samples and d_var are all NULL"
+                                                           : ": d_rgba, d_mean and d_samples are all NULL"));
   if (int rc = cam_out_check(d_rgba, d_mean, who); rc != RT_OK) return rc;
   if (((uintptr_t)d_samples & 3) != 0)
     return fail(RT_E_INVALID, std::string(who) + ": d_samples must be 4-byte aligned");
+  if (int rc = cam_var_check(d_var, P.A.S, who); rc != RT_OK) return rc;
   const DevScene& s = c->sc;
   DeviceGuard guard(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -615,6 +709,7 @@ int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const r
       R.rgba = (uint32_t*)d_rgba;
       R.mean = d_mean;
       R.samples = d_samples;
+      R.var = d_var;
       void* rargs[] = {(void*)&R};
       HIP_TRY(hipLaunchKernel((const void*)cam_adapt_kernel, dim3((unsigned)((npix + WG - 1) / WG)), dim3(WG), rargs, 0,
                               st));
@@ -622,6 +717,23 @@ int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const r
   }
   HIP_TRY(hipGetLastError());
   return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render_camera_adaptive_async(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1,
+                                    void* d_rgba, double* d_mean, int32_t* d_samples, void* stream) {
+  return cam_render_adaptive(c, cam, ad, y0, y1, d_rgba, d_mean, d_samples, nullptr, stream,
+                             "rt_render_camera_adaptive_async", false);
+}
+
+int rt_render_camera_adaptive_var_async(rt_context* c, const rt_camera* cam, const rt_adaptive* ad, int y0, int y1,
+                                        void* d_rgba, double* d_mean, int32_t* d_samples, double* d_var,
+                                        void* stream) {
+  return cam_render_adaptive(c, cam, ad, y0, y1, d_rgba, d_mean, d_samples, d_var, stream,
+                             "rt_render_camera_adaptive_var_async", true);
 }
 
 }  // extern "C"

@@ -18,6 +18,10 @@ LIB_PATH = os.path.join(PKG_DIR, "csrc", "librtamd.so")
 _lib = None
 # sigmas RenderContext.denoise and the CLI use when none are given (README "Denoising")
 DENOISE_DEFAULTS = {"color": 0.6, "normal": 0.5, "depth": 1.0, "albedo": 0.25}
+# the colour sigma, in standard deviations, of the variance-guided mode (RenderContext.denoise with `var`): the
+# best of 1, 2, 4, 8 on the measured frame (BASELINE.md "Measured: variance and the variance-guided filter");
+# SVGF's published 4 came second
+DENOISE_VAR_COLOR = 8.0
 
 
 class RenderError(RuntimeError):
@@ -117,6 +121,12 @@ def load_library(path=None):
     l.rt_render_camera_aov_async.restype = i
     l.rt_denoise_atrous_async.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
     l.rt_denoise_atrous_async.restype = i
+    l.rt_render_camera_var_async.argtypes = [vp, vp, i, i, vp, vp, vp, vp]
+    l.rt_render_camera_var_async.restype = i
+    l.rt_render_camera_adaptive_var_async.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp, vp]
+    l.rt_render_camera_adaptive_var_async.restype = i
+    l.rt_denoise_atrous_var_async.argtypes = [vp, vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    l.rt_denoise_atrous_var_async.restype = i
     if l.rt_abi_version() != abi.RT_ABI_VERSION:
         raise RenderError("librtamd ABI version mismatch")
     _lib = l
@@ -500,17 +510,22 @@ class RenderContext:
         torch.cuda.synchronize(self.device)
         return out.cpu().numpy().view(abi.RAY_DTYPE).reshape(rows, w, S)
 
-    def render_camera_async(self, cam, y0, y1, rgba=None, mean=None, stream=None):
+    def render_camera_async(self, cam, y0, y1, rgba=None, mean=None, stream=None, var=None):
         """Enqueue the camera render of rows [y0, y1) of `cam`'s frame (None:
         the zero camera, Render()'s pixels) into either or both of `rgba`, a
         uint8 CUDA tensor [rows, W, 4], and `mean`, a float64 CUDA tensor
-        [rows, W, 3] (the mean radiance before quantisation). Camera renders
+        [rows, W, 3] (the mean radiance before quantisation). `var`, a float64
+        CUDA tensor [rows, W, 3], receives the variance of each pixel's mean
+        (rt_render_camera_var_async; needs at least 2 samples). Camera renders
         and radiance queries on one context share a workspace: keep them
         ordered with respect to each other."""
         torch = self.torch
         cam, w, _, _ = self._camera_frame(cam)
         rows = max(0, int(y1) - int(y0))
         rp = mp = None
+        if var is not None:
+            assert var.dtype == torch.float64, "render_camera_async: var must be a float64 tensor"
+            vp = self._camera_out(var, rows * w * 24, "render_camera_async", "var")
         if rgba is not None:
             assert rgba.dtype == torch.uint8, "render_camera_async: rgba must be a uint8 tensor"
             rp = self._camera_out(rgba, rows * w * 4, "render_camera_async", "rgba")
@@ -518,12 +533,18 @@ class RenderContext:
             assert mean.dtype == torch.float64, "render_camera_async: mean must be a float64 tensor"
             mp = self._camera_out(mean, rows * w * 24, "render_camera_async", "mean")
         s = torch.cuda.current_stream(self.device) if stream is None else stream
+        if var is not None:
+            _check(self.lib.rt_render_camera_var_async(self.handle, C.byref(cam), int(y0), int(y1), rp, mp, vp,
+                                                       C.c_void_p(s.cuda_stream)), "rt_render_camera_var_async")
+            return
         _check(self.lib.rt_render_camera_async(self.handle, C.byref(cam), int(y0), int(y1), rp, mp,
                                                C.c_void_p(s.cuda_stream)), "rt_render_camera_async")
 
-    def render_camera(self, cam=None, y0=0, y1=None, mean=False):
+    def render_camera(self, cam=None, y0=0, y1=None, mean=False, var=False):
         """Synchronous camera render of rows [y0, y1) -> numpy uint8 [rows, W,
-        4]; with mean=True -> (that, float64 [rows, W, 3] mean radiance)."""
+        4]; with mean=True and / or var=True -> a tuple of that, the float64
+        [rows, W, 3] mean radiance and the float64 [rows, W, 3] variance of
+        that mean, in this order."""
         torch = self.torch
         cam, w, h, _ = self._camera_frame(cam)
         if y1 is None:
@@ -532,9 +553,11 @@ class RenderContext:
         dev = "cuda:%d" % self.device
         rgba = torch.empty((rows, w, 4), dtype=torch.uint8, device=dev)
         m = torch.empty((rows, w, 3), dtype=torch.float64, device=dev) if mean else None
-        self.render_camera_async(cam, y0, y1, rgba, m)
+        v = torch.empty((rows, w, 3), dtype=torch.float64, device=dev) if var else None
+        self.render_camera_async(cam, y0, y1, rgba, m, var=v)
         torch.cuda.synchronize(self.device)
-        return (rgba.cpu().numpy(), m.cpu().numpy()) if mean else rgba.cpu().numpy()
+        out = [t.cpu().numpy() for t in (rgba, m, v) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def render_camera_chunks(self, cam=None, y0=0, y1=None):
         """Launches of the radiance kernel render_camera_async makes for these arguments."""
@@ -555,11 +578,14 @@ class RenderContext:
         ad.min_samples = int(min_samples)
         return ad
 
-    def render_camera_adaptive_async(self, cam, ad, y0, y1, rgba=None, mean=None, samples=None, stream=None):
+    def render_camera_adaptive_async(self, cam, ad, y0, y1, rgba=None, mean=None, samples=None, stream=None,
+                                     var=None):
         """Enqueue the adaptive camera render of rows [y0, y1) of `cam`'s
         frame, whose samples are the cap, into any of `rgba` (uint8 [rows, W,
         4]), `mean` (float64 [rows, W, 3]) and `samples` (int32 [rows, W]: the
-        samples each pixel took), all CUDA tensors. Ordering as
+        samples each pixel took) and `var` (float64 [rows, W, 3]: the variance
+        of each pixel's mean at the count it ends with;
+        rt_render_camera_adaptive_var_async), all CUDA tensors. Ordering as
         render_camera_async."""
         torch = self.torch
         who = "render_camera_adaptive_async"
@@ -576,15 +602,23 @@ class RenderContext:
             assert samples.dtype == torch.int32, who + ": samples must be an int32 tensor"
             sp = self._camera_out(samples, rows * w * 4, who, "samples")
         s = torch.cuda.current_stream(self.device) if stream is None else stream
+        if var is not None:
+            assert var.dtype == torch.float64, who + ": var must be a float64 tensor"
+            vp = self._camera_out(var, rows * w * 24, who, "var")
+            _check(self.lib.rt_render_camera_adaptive_var_async(self.handle, C.byref(cam), C.byref(ad), int(y0),
+                                                                int(y1), rp, mp, sp, vp, C.c_void_p(s.cuda_stream)),
+                   "rt_render_camera_adaptive_var_async")
+            return
         _check(self.lib.rt_render_camera_adaptive_async(self.handle, C.byref(cam), C.byref(ad), int(y0), int(y1), rp, mp,
                                                         sp, C.c_void_p(s.cuda_stream)),
                "rt_render_camera_adaptive_async")
 
-    def render_camera_adaptive(self, cam, ad, y0=0, y1=None, mean=False, samples=False):
+    def render_camera_adaptive(self, cam, ad, y0=0, y1=None, mean=False, samples=False, var=False):
         """Synchronous adaptive camera render of rows [y0, y1) -> numpy uint8
-        [rows, W, 4]; with mean=True and / or samples=True -> a tuple of that,
-        the float64 [rows, W, 3] mean radiance and the int32 [rows, W] sample
-        counts, in this order."""
+        [rows, W, 4]; with mean=True, samples=True and / or var=True -> a
+        tuple of that, the float64 [rows, W, 3] mean radiance, the int32
+        [rows, W] sample counts and the float64 [rows, W, 3] variance of the
+        mean, in this order."""
         torch = self.torch
         cam, w, h, _ = self._camera_frame(cam)
         if y1 is None:
@@ -594,9 +628,10 @@ class RenderContext:
         rgba = torch.empty((rows, w, 4), dtype=torch.uint8, device=dev)
         m = torch.empty((rows, w, 3), dtype=torch.float64, device=dev) if mean else None
         n = torch.empty((rows, w), dtype=torch.int32, device=dev) if samples else None
-        self.render_camera_adaptive_async(cam, ad, y0, y1, rgba, m, n)
+        v = torch.empty((rows, w, 3), dtype=torch.float64, device=dev) if var else None
+        self.render_camera_adaptive_async(cam, ad, y0, y1, rgba, m, n, var=v)
         torch.cuda.synchronize(self.device)
-        out = [t.cpu().numpy() for t in (rgba, m, n) if t is not None]
+        out = [t.cpu().numpy() for t in (rgba, m, n, v) if t is not None]
         return out[0] if len(out) == 1 else tuple(out)
 
     def render_camera_adaptive_plan(self, cam, ad, y0=0, y1=None):
@@ -671,17 +706,24 @@ class RenderContext:
         return dn
 
     def denoise_async(self, params, color, out, tmp=None, normal=None, depth=None, albedo=None, rgba=None,
-                      stream=None):
+                      stream=None, var=None, var_out=None, var_tmp=None):
         """Enqueue the a-trous filter of the whole frame `color` (float64 CUDA
         tensor [H, W, 3], never written) into `out` (same shape), one launch
         per iteration. `tmp` (same shape) is needed for more than one
         iteration; the guides `normal` [H, W, 3], `depth` [H, W] and `albedo`
         [H, W, 3] are needed where their term is on; `rgba` (uint8 [H, W, 4])
-        optionally receives the quantised result. Needs no scene."""
+        optionally receives the quantised result. Needs no scene.
+        Giving `var` (float64 [H, W, 3], the variance of `color`, never
+        written) selects the variance-guided filter
+        (rt_denoise_atrous_var_async): params.sigma_color is then in standard
+        deviations, and `var_out` and `var_tmp` (float64 [H, W]) are both
+        needed; `var_out` receives the filtered frame's variance estimate."""
         torch = self.torch
         who = "denoise_async"
         assert color.dim() == 3 and color.shape[2] == 3, who + ": color must be [H, W, 3]"
         h, w = int(color.shape[0]), int(color.shape[1])
+        assert var is not None or (var_out is None and var_tmp is None), who + ": var_out and var_tmp need var"
+        assert var is None or (var_out is not None and var_tmp is not None), who + ": var needs var_out and var_tmp"
         ptrs = []
         for name, t, per in (("color", color, 3), ("normal", normal, 3), ("depth", depth, 1), ("albedo", albedo, 3),
                              ("out", out, 3), ("tmp", tmp, 3)):
@@ -695,19 +737,39 @@ class RenderContext:
             assert rgba.dtype == torch.uint8, who + ": rgba must be a uint8 tensor"
             rp = self._camera_out(rgba, h * w * 4, who, "rgba")
         s = torch.cuda.current_stream(self.device) if stream is None else stream
+        if var is not None:
+            vps = []
+            for name, t, per in (("var", var, 3), ("var_out", var_out, 1), ("var_tmp", var_tmp, 1)):
+                assert t.dtype == torch.float64, "%s: %s must be a float64 tensor" % (who, name)
+                vps.append(self._camera_out(t, h * w * per * 8, who, name))
+            _check(self.lib.rt_denoise_atrous_var_async(self.handle, C.byref(params), w, h, ptrs[0], vps[0], *ptrs[1:],
+                                                        vps[1], vps[2], rp, C.c_void_p(s.cuda_stream)),
+                   "rt_denoise_atrous_var_async")
+            return
         _check(self.lib.rt_denoise_atrous_async(self.handle, C.byref(params), w, h, *ptrs, rp,
                                                 C.c_void_p(s.cuda_stream)), "rt_denoise_atrous_async")
 
-    def denoise(self, mean, normal=None, depth=None, albedo=None, params=None, rgba=False):
+    def denoise(self, mean, normal=None, depth=None, albedo=None, params=None, rgba=False, var=None,
+                variance_out=False):
         """Synchronous a-trous filter of a numpy float64 [H, W, 3] mean with
         the given guides (numpy arrays as render_camera_aov returns them) ->
         float64 [H, W, 3]; with rgba=True -> (that, uint8 [H, W, 4]). `params`
-        None: denoise_params() with DENOISE_DEFAULTS for the guides given."""
+        None: denoise_params() with DENOISE_DEFAULTS for the guides given.
+        Giving `var`, the float64 [H, W, 3] variance of `mean` as
+        render_camera(var=True) returns it, selects the variance-guided
+        filter: the colour sigma is then in standard deviations (`params`
+        None: DENOISE_VAR_COLOR), and variance_out=True appends the filtered
+        frame's float64 [H, W] variance estimate to the result."""
         torch = self.torch
         dev = "cuda:%d" % self.device
+        if var is None and variance_out:
+            raise ValueError("denoise: variance_out needs var")
+        if var is not None and np.shape(var) != np.shape(mean):
+            raise ValueError("denoise: var must have the shape of mean")
         if params is None:
             d = DENOISE_DEFAULTS
-            params = self.denoise_params(0, d["color"], d["normal"] if normal is not None else 0.0,
+            params = self.denoise_params(0, d["color"] if var is None else DENOISE_VAR_COLOR,
+                                         d["normal"] if normal is not None else 0.0,
                                          d["depth"] if depth is not None else 0.0,
                                          d["albedo"] if albedo is not None else 0.0)
 
@@ -719,9 +781,19 @@ class RenderContext:
         k = int(params.iterations) or 5
         tmp = torch.empty_like(color) if k > 1 else None
         img = torch.empty(tuple(color.shape[:2]) + (4,), dtype=torch.uint8, device=dev) if rgba else None
-        self.denoise_async(params, color, out, tmp, up(normal), up(depth), up(albedo), img)
+        vo = vt = None
+        if var is not None:
+            vo = torch.empty(tuple(color.shape[:2]), dtype=torch.float64, device=dev)
+            vt = torch.empty_like(vo)
+        self.denoise_async(params, color, out, tmp, up(normal), up(depth), up(albedo), img, var=up(var), var_out=vo,
+                           var_tmp=vt)
         torch.cuda.synchronize(self.device)
-        return (out.cpu().numpy(), img.cpu().numpy()) if rgba else out.cpu().numpy()
+        res = [out.cpu().numpy()]
+        if rgba:
+            res.append(img.cpu().numpy())
+        if variance_out:
+            res.append(vo.cpu().numpy())
+        return res[0] if len(res) == 1 else tuple(res)
 
     def image_from_radiance(self, out, samples):
         """Average `samples` consecutive radiance records per pixel and quantise

@@ -733,6 +733,33 @@ int rt_render_camera_adaptive_async(rt_context *ctx, const rt_camera *cam, const
 int rt_render_camera_adaptive_plan(rt_context *ctx, const rt_camera *cam, const rt_adaptive *ad, int y0, int y1,
                                    int *chunks, int *passes);
 
+/* ---- Variance of a camera render: the squared standard error of each pixel's
+ * mean, per channel ---- (csrc/rt_camera.hip). FP64, one rounding per
+ * operation, no contraction, in the order written here; the state and the
+ * expressions are those of "Adaptive camera renders" above, unchanged.
+ * Sum_c and Q_c accumulate in sample order over the pixel's n samples (Sum_c
+ * and Q_c start as c_0 and c_0 * c_0; then Sum_c = Sum_c + c_s and
+ * Q_c = Q_c + (c_s * c_s)): n = S for the fixed render, and the count the
+ * pixel ends with for the adaptive render. Then
+ *   inv = 1.0 / (double)n;  m_c = Sum_c * inv;  v_c = Q_c - Sum_c * m_c;
+ *   e_c = v_c / (double)(n * (n - 1));  var_c = e_c < 0.0 ? 0.0 : e_c
+ * so a negative estimate becomes 0 and a NaN stays NaN. m_c is bit for bit the
+ * mean the calls without a variance write.
+ * d_var holds 3 doubles per pixel, 8-byte aligned, laid out like d_mean. With
+ * d_var == NULL the two calls below are rt_render_camera_async and
+ * rt_render_camera_adaptive_async: the same checks, chunks, launches (the
+ * same kernels), memory, ordering and side effects. With a d_var the fixed
+ * render's resolve launch is a sibling kernel that also keeps Q_c, and the
+ * adaptive render's per-pass launch writes var_c where it writes m_c; d_rgba
+ * and d_mean receive what those calls write. RT_E_INVALID in addition to those
+ * calls' cases: all outputs NULL (d_var included), d_var not 8-byte aligned,
+ * d_var given with samples == 1 (there is no estimate from one sample). */
+int rt_render_camera_var_async(rt_context *ctx, const rt_camera *cam, int y0, int y1,
+                               void *d_rgba, double *d_mean, double *d_var, void *stream);
+int rt_render_camera_adaptive_var_async(rt_context *ctx, const rt_camera *cam, const rt_adaptive *ad, int y0, int y1,
+                                        void *d_rgba, double *d_mean, int32_t *d_samples,
+                                        double *d_var, void *stream);
+
 /* ---- Feature buffers: per-pixel depth, normal, albedo, coverage and ids of a
  * camera render, and an edge-avoiding a-trous filter guided by them ----
  * (csrc/rt_aov.hip). Everything is FP64, one rounding per operation, no
@@ -820,6 +847,50 @@ typedef struct rt_denoise {
 int rt_denoise_atrous_async(rt_context *ctx, const rt_denoise *dn, int width, int height,
                             const double *d_color, const double *d_normal, const double *d_depth,
                             const double *d_albedo, double *d_out, double *d_tmp, void *d_rgba, void *stream);
+
+/* ---- Variance-guided a-trous filter ---- (csrc/rt_aov.hip). The filter above
+ * with its colour term scaled by the locally prefiltered standard deviation of
+ * the pixel, and a scalar variance carried through the iterations (as SVGF
+ * does). rt_denoise is reused unchanged; in this call sigma_color is in
+ * standard deviations. FP64, one rounding per operation, in this order.
+ * Taps, kern, dist2, the normal, depth and albedo terms, the d_out / d_tmp
+ * ping-pong, the buffer sizes, K and the rule that turns a term on or off are
+ * exactly those of rt_denoise_atrous_async. d_var (3 doubles per pixel, as
+ * rt_render_camera_var_async writes it) is the variance of d_color.
+ * The scalar variance S_i has one double per pixel and lives in d_var_out when
+ * K - i is even, else in d_var_tmp (both are always needed); S_K ends in
+ * d_var_out, the filtered frame's variance estimate. One reduce launch writes
+ *   S_0[p] = (var[p].0 + var[p].1) + var[p].2
+ * kc2 = sigma_color * sigma_color is formed on the host; sigma does not halve
+ * per iteration.
+ * Iteration i at pixel p = (x, y), with the colour term on: g = N / D with
+ * N = 0, D = 0 and, for dy = -1..1 (outer), dx = -1..1 (inner) at unit spacing
+ * whatever the step, q = (x + dx, y + dy) skipped when outside the frame,
+ * k = (1/4, 1/2, 1/4):
+ *   N = N + (k[dy + 1] * k[dx + 1]) * S_i[q];  D = D + k[dy + 1] * k[dx + 1]
+ * then icv = 1.0 / (kc2 * g + RT_DENOISE_VAR_EPS), and the colour term of tap
+ * q is  w = w * kern(dist2(I_i[p], I_i[q]) * icv); the guides follow in the
+ * old order. A tap with w > 0.0 contributes to sum and wsum as before and also
+ *   vs = vs + (w * w) * S_i[q]          (vs starts at 0)
+ * I_(i+1)[p] is formed as before, and
+ *   S_(i+1)[p] = wsum > 0.0 ? vs / (wsum * wsum) : S_i[p]
+ * With the colour term off no g is formed and the variance still propagates.
+ * A NaN g shuts every tap: the pixel and its variance pass through. g = +inf
+ * opens the colour term fully (icv = 0). */
+#define RT_DENOISE_VAR_EPS 1e-10
+
+/* One reduce launch, then one launch per iteration on `stream`; the host never
+ * waits, nothing is allocated, and d_color and d_var are never written.
+ * RT_E_INVALID as for rt_denoise_atrous_async, and: NULL or not 8-byte aligned
+ * d_var, d_var_out or d_var_tmp; any overlap among the byte ranges of d_color,
+ * d_var, d_out, d_tmp (3 doubles per pixel each), d_var_out and d_var_tmp (1
+ * double per pixel each). d_tmp may still be NULL when there is one
+ * iteration. Nothing is launched then. */
+int rt_denoise_atrous_var_async(rt_context *ctx, const rt_denoise *dn, int width, int height,
+                                const double *d_color, const double *d_var,
+                                const double *d_normal, const double *d_depth, const double *d_albedo,
+                                double *d_out, double *d_tmp, double *d_var_out, double *d_var_tmp,
+                                void *d_rgba, void *stream);
 
 /* SSIM of two RGBA8 frames in device memory (width x height, stride 4W), the
  * reference's parity metric prim.SSIM (internal/prim/ssim.go:27-182; used by

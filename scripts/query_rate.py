@@ -54,10 +54,24 @@ floor (104 B per pixel at 8 TB/s) and the FP64 floor (1.1 k operations per
 pixel at 78.6 TFLOP/s); at 1080p also the mean squared error of the raw and of
 the denoised mean against a 256-sample mean for a few sigma sets.
 
+Variance mode (not in the default modes; writes
+profiles/variance/variance_rate.jsonl unless --out says otherwise), device
+events, one warm-up, the median of 5: rt_render_camera_var_async with and
+without d_var at 1920x1080 x 4 and x 64 samples, and
+rt_render_camera_adaptive_var_async likewise (tolerance 0.005, cap 64);
+rt_denoise_atrous_async beside rt_denoise_atrous_var_async per call and per
+iteration at 1920x1080 and 3840x2160, with the memory floor (104 + 16 B per
+pixel at 8 TB/s) and the FP64 floor (1.2 k operations per pixel); and the mean
+squared error against a 256-sample mean of the 4-sample thin-lens frame: raw,
+the plain filter at its defaults and colour-only, the variance-guided filter
+at 1, 2, 4 and 8 standard deviations with and without the guides, and one
+adaptive frame (tolerance 0.005, cap 64) filtered with its own variance.
+
 usage: python scripts/query_rate.py [--configs c3,c4csg,c5]
-                                    [--modes closest,occluded,radiance,camera,adaptive,aov,denoise] [--out FILE]
+                                    [--modes closest,occluded,radiance,camera,adaptive,aov,denoise,variance] [--out FILE]
 """
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -366,6 +380,136 @@ def denoise_lines(torch, abi, ctx, name, seed, default_sigmas):
     return lines
 
 
+VAR_SIGMAS = (1.0, 2.0, 4.0, 8.0)
+VAR_COLOR = 8.0  # render.DENOISE_VAR_COLOR, set by main()
+DN_VAR_BYTES_PER_PIXEL, DN_VAR_FLOP_PER_PIXEL = DN_BYTES_PER_PIXEL + 16, 1200  # S_i read and S_(i+1) written; 4 ops a tap
+
+
+def variance_lines(torch, abi, ctx, name, seed, defaults):
+    """The cost of the variance outputs, the time of the variance-guided
+    filter beside the plain one, and both filters' error against a 256-sample
+    mean (module docstring, "Variance mode")."""
+    dev = "cuda:0"
+    med = lambda v: round(float(np.median(v)), 4)  # noqa: E731
+    r4 = lambda v: [round(x, 4) for x in v]  # noqa: E731
+    base = {"config": name, "mode": "variance", "repeats": AOV_REPEATS, "warmup": 1, "seed": seed}
+    lines = []
+    # 1. the renders with and without d_var (both through the new entry points: d_var NULL is the old call)
+    lib = ctx.lib
+    mean = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+    var = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+    cnt = torch.empty((H, W), dtype=torch.int32, device=dev)
+    vp = ctypes.c_void_p
+    stream = lambda: vp(torch.cuda.current_stream(0).cuda_stream)  # noqa: E731
+    for S in AOV_SAMPLES:
+        cam = ctx.camera(samples=S)
+
+        def fixed(v):
+            rc = lib.rt_render_camera_var_async(ctx.handle, ctypes.byref(cam), 0, H, None, vp(mean.data_ptr()), v, stream())
+            assert rc == 0, lib.rt_last_error()
+
+        without = repeats(torch, lambda: fixed(None), 1, AOV_REPEATS)
+        with_ = repeats(torch, lambda: fixed(vp(var.data_ptr())), 1, AOV_REPEATS)
+        lines.append(dict(base, metric="variance_cost", call="rt_render_camera_var_async", width=W, height=H, samples=S,
+                          without_var_ms=r4(without), with_var_ms=r4(with_), without_median_ms=med(without),
+                          with_median_ms=med(with_), with_over_without=round(med(with_) / med(without), 4),
+                          without_spread_ms=round(max(without) - min(without), 4)))
+    cam = ctx.camera(samples=64)
+    ad = ctx.adaptive(0.005, 4)
+
+    def adaptive(v):
+        rc = lib.rt_render_camera_adaptive_var_async(ctx.handle, ctypes.byref(cam), ctypes.byref(ad), 0, H, None,
+                                                     vp(mean.data_ptr()), vp(cnt.data_ptr()), v, stream())
+        assert rc == 0, lib.rt_last_error()
+
+    without = repeats(torch, lambda: adaptive(None), 1, AOV_REPEATS)
+    with_ = repeats(torch, lambda: adaptive(vp(var.data_ptr())), 1, AOV_REPEATS)
+    lines.append(dict(base, metric="variance_cost", call="rt_render_camera_adaptive_var_async", width=W, height=H,
+                      samples=64, min_samples=4, tolerance=0.005, mean_samples=round(float(cnt.double().mean().item()), 3),
+                      without_var_ms=r4(without), with_var_ms=r4(with_), without_median_ms=med(without),
+                      with_median_ms=med(with_), with_over_without=round(med(with_) / med(without), 4),
+                      without_spread_ms=round(max(without) - min(without), 4)))
+    del mean, var, cnt
+    # 2. the filters' time, 3. their error
+    for (w, h) in DN_SIZES:
+        kw = dict(model="thinlens", size=(w, h), aperture=0.2, focus=4.5)
+        cam = ctx.camera(samples=4, **kw)
+        mean = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+        var = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+        ctx.render_camera_async(cam, 0, h, mean=mean, var=var)
+        g = {"normal": torch.empty((h, w, 3), dtype=torch.float64, device=dev),
+             "depth": torch.empty((h, w), dtype=torch.float64, device=dev),
+             "albedo": torch.empty((h, w, 3), dtype=torch.float64, device=dev)}
+        ctx.render_camera_aov_async(cam, 0, h, **g)
+        out, tmp = torch.empty_like(mean), torch.empty_like(mean)
+        vo = torch.empty((h, w), dtype=torch.float64, device=dev)
+        vt = torch.empty_like(vo)
+        vkw = dict(var=var, var_out=vo, var_tmp=vt)
+        guides = tuple(defaults[1:])
+        vsig = (VAR_COLOR,) + guides
+        plain = repeats(torch, lambda: ctx.denoise_async(ctx.denoise_params(5, *defaults), mean, out, tmp, **g), 1, AOV_REPEATS)
+        guided = repeats(torch, lambda: ctx.denoise_async(ctx.denoise_params(5, *vsig), mean, out, tmp, **g, **vkw), 1,
+                         AOV_REPEATS)
+        firstk = {"plain": [], "variance": []}
+        for i in range(5):  # the first i + 1 iterations (a later iteration cannot be launched alone)
+            dk, dv = ctx.denoise_params(i + 1, *defaults), ctx.denoise_params(i + 1, *vsig)
+            firstk["plain"].append(med(repeats(torch, lambda: ctx.denoise_async(dk, mean, out, tmp, **g), 1, 3)))
+            firstk["variance"].append(med(repeats(torch, lambda: ctx.denoise_async(dv, mean, out, tmp, **g, **vkw), 1, 3)))
+        px = w * h
+        line = dict(base, metric="denoise_var_rate", width=w, height=h, iterations=5, plain_sigmas=list(defaults),
+                    variance_sigmas=list(vsig), plain_ms=r4(plain), variance_ms=r4(guided), plain_call_ms=med(plain),
+                    variance_call_ms=med(guided), plain_ms_per_iteration=round(med(plain) / 5, 4),
+                    variance_ms_per_iteration=round(med(guided) / 5, 4),
+                    variance_over_plain=round(med(guided) / med(plain), 4), first_k_iterations_ms=firstk,
+                    plain_floor_memory_ms=round(px * DN_BYTES_PER_PIXEL / DN_HBM_BYTES_PER_S * 1e3, 4),
+                    plain_floor_fp64_ms=round(px * DN_FLOP_PER_PIXEL / DN_FP64_FLOPS * 1e3, 4),
+                    variance_floor_memory_ms=round(px * DN_VAR_BYTES_PER_PIXEL / DN_HBM_BYTES_PER_S * 1e3, 4),
+                    variance_floor_fp64_ms=round(px * DN_VAR_FLOP_PER_PIXEL / DN_FP64_FLOPS * 1e3, 4))
+        if (w, h) == DN_SIZES[0]:
+            ref = torch.empty_like(mean)
+            ctx.render_camera_async(ctx.camera(samples=256, **kw), 0, h, mean=ref)
+            torch.cuda.synchronize()
+            mse = lambda t: float(((t - ref) ** 2).mean().item())  # noqa: E731
+
+            def run(sig, m, v=None):
+                kv = dict(var=v, var_out=vo, var_tmp=vt) if v is not None else {}
+                gg = {k: t for k, t, sg in (("normal", g["normal"], sig[1]), ("depth", g["depth"], sig[2]),
+                                            ("albedo", g["albedo"], sig[3])) if sg > 0.0}
+                ctx.denoise_async(ctx.denoise_params(5, *sig), m, out, tmp, **gg, **kv)
+                torch.cuda.synchronize()
+                return mse(out)
+
+            q = [{"filter": "raw", "mse_vs_256": mse(mean)},
+                 {"filter": "plain", "sigmas": list(defaults), "mse_vs_256": run(defaults, mean)},
+                 {"filter": "plain", "sigmas": [defaults[0], 0.0, 0.0, 0.0],
+                  "mse_vs_256": run((defaults[0], 0.0, 0.0, 0.0), mean)}]
+            for sc in VAR_SIGMAS:
+                for gs in (guides, (0.0, 0.0, 0.0)):
+                    q.append({"filter": "variance", "sigmas": [sc] + list(gs), "mse_vs_256": run((sc,) + gs, mean, var)})
+            line["quality"] = q
+            line["mean_variance"] = float(var.sum(dim=2).mean().item())
+            # one adaptive frame filtered with its own variance
+            acam = ctx.camera(samples=64, **kw)
+            amean, avar = torch.empty_like(mean), torch.empty_like(var)
+            acnt = torch.empty((h, w), dtype=torch.int32, device=dev)
+            ctx.render_camera_adaptive_async(acam, ctx.adaptive(0.005, 4), 0, h, mean=amean, samples=acnt, var=avar)
+            torch.cuda.synchronize()
+            qa = [{"filter": "raw", "mse_vs_256": mse(amean)},
+                  {"filter": "plain", "sigmas": list(defaults), "mse_vs_256": run(defaults, amean)},
+                  {"filter": "plain", "sigmas": [defaults[0], 0.0, 0.0, 0.0],
+                   "mse_vs_256": run((defaults[0], 0.0, 0.0, 0.0), amean)}]
+            for sc in VAR_SIGMAS:
+                for gs in (guides, (0.0, 0.0, 0.0)):
+                    qa.append({"filter": "variance", "sigmas": [sc] + list(gs),
+                               "mse_vs_256": run((sc,) + gs, amean, avar)})
+            line["adaptive"] = {"tolerance": 0.005, "min_samples": 4, "cap": 64,
+                                "mean_samples": round(float(acnt.double().mean().item()), 3), "quality": qa}
+            del ref, amean, avar, acnt
+        lines.append(line)
+        del mean, var, out, tmp, vo, vt, g
+    return lines
+
+
 def camera_rays(fov_deg, seed):
     g = np.random.default_rng(seed)
     vw = 2.0 * math.tan(math.radians(fov_deg) / 2.0)
@@ -437,7 +581,19 @@ def main():
             for ln in denoise_lines(torch, abi, ctx, name, args.seed, (d["color"], d["normal"], d["depth"], d["albedo"])):
                 lines.append(ln)
                 print(json.dumps(ln), flush=True)
+        if "variance" in modes:
+            d = pkg.render.DENOISE_DEFAULTS
+            global VAR_COLOR
+            VAR_COLOR = pkg.render.DENOISE_VAR_COLOR
+            for ln in variance_lines(torch, abi, ctx, name, args.seed, (d["color"], d["normal"], d["depth"], d["albedo"])):
+                lines.append(ln)
+                print(json.dumps(ln), flush=True)
     ctx.close()
+    if args.out is None and "variance" in args.modes.split(","):
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "variance",
+                                "variance_rate.jsonl")
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        lines = [ln for ln in lines if ln["mode"] == "variance"]
     if args.out is None and ("aov" in args.modes.split(",") or "denoise" in args.modes.split(",")):
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "aov",
                                 "aov_rate.jsonl")
