@@ -331,6 +331,8 @@ bool axis_sphere(const double* m) {
 enum { BVH_MIN = 12,          // scenes with at least this many bounded objects use the BVH flavour
        BVH_LEAF = 4,          // objects per BVH leaf (<= 7: the leaf ref holds the count in 3 bits)
        FAR_MIN_OBJ = 1024 };  // BVH scenes from this many objects keep the far-origin shift when specialised
+// |o2w|_F |w2o|_F above which an object's bounding sphere is not trusted (rt_set_scene)
+constexpr double NEEDLE_COND = 1e6;
 
 float f_down(double x) {
   float f = (float)x;
@@ -1721,13 +1723,26 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
         cmax = std::max(cmax, std::fabs(cc[r]));
       }
       double rad = fro * lr[o.kind] * 1.0001 + 1e-4 * (1.0 + cmax + fro);
+      // An ill-conditioned transform: the exact test works with w2o, the
+      // cofactor inverse, and from |o2w|_F |w2o|_F = 1e8 it reports hit points
+      // up to two radii outside this sphere (measured on the oracle:
+      // tests/cull_limits.py NEEDLE_FIRST_OUTSIDE; none up to 1e7). From one
+      // decade of scale below that the object is never culled: an infinite
+      // radius (may_hit's `<= inf` holds for every finite or overflowed left
+      // side) around centre 0, and a place among the unbounded objects beside
+      // the planes. The bound is strict on the safe side: scale(1/s, 1, s) at
+      // s = 1e3 has condition 1e6 + 1 and already counts as ill-conditioned.
+      double fri = 0.0;
+      for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++) fri += w2o.m[r][k] * w2o.m[r][k];
+      const bool needle = !(fro * std::sqrt(fri) <= NEEDLE_COND);
       float* b = reinterpret_cast<float*>(&g[12]);
-      b[0] = (float)cc[0];
-      b[1] = (float)cc[1];
-      b[2] = (float)cc[2];
-      b[3] = f_up(rad);
+      b[0] = needle ? 0.0f : (float)cc[0];
+      b[1] = needle ? 0.0f : (float)cc[1];
+      b[2] = needle ? 0.0f : (float)cc[2];
+      b[3] = needle ? std::numeric_limits<float>::infinity() : f_up(rad);
       for (int k = 0; k < 3; k++) bcen[(size_t)i * 3 + k] = cc[k];
-      brad[i] = rad;
+      brad[i] = needle ? std::numeric_limits<double>::infinity() : rad;
     }
     if (o.kind == RT_PLANE) {
       double nw[3], dv;
@@ -1784,7 +1799,7 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
       if (op >= 0) {
         const int li = s.nobj + o.csg_first + op;
         Bd b;
-        b.fin = kind[li] != RT_PLANE;
+        b.fin = kind[li] != RT_PLANE && std::isfinite(brad[li]);
         for (int q = 0; q < 3; q++) b.c[q] = bcen[(size_t)li * 3 + q];
         b.r = brad[li];
         st.push_back(b);
@@ -1839,7 +1854,8 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
       std::vector<std::vector<int>> groups;
       std::vector<int> bounded_l, plane_l;
       for (int j = 0; j < o.csg_count; j++)
-        (kind[s.nobj + o.csg_first + j] == RT_PLANE ? plane_l : bounded_l).push_back(j);
+        (kind[s.nobj + o.csg_first + j] == RT_PLANE || !std::isfinite(brad[s.nobj + o.csg_first + j]) ? plane_l : bounded_l)
+            .push_back(j);
       if (o.csg_count >= CSG_GROUP_MIN) {
         std::function<void(std::vector<int>)> split = [&](std::vector<int> v) {
           if (v.size() <= 8) {
@@ -1874,13 +1890,13 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
         double c[3] = {0, 0, 0}, lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
         for (int j : gv) {
           const int li = s.nobj + o.csg_first + j;
-          if (kind[li] == RT_PLANE) fin = false;
+          if (kind[li] == RT_PLANE || !std::isfinite(brad[li])) fin = false;
           for (int q = 0; q < 3; q++) {
             lo[q] = std::min(lo[q], bcen[(size_t)li * 3 + q] - brad[li]);
             hi[q] = std::max(hi[q], bcen[(size_t)li * 3 + q] + brad[li]);
           }
         }
-        for (int q = 0; q < 3; q++) c[q] = 0.5 * (lo[q] + hi[q]);
+        for (int q = 0; q < 3; q++) c[q] = fin ? 0.5 * (lo[q] + hi[q]) : 0.0;  // (a never-culled group: a finite centre)
         double rr = 0.0;
         for (int j : gv) {
           const int li = s.nobj + o.csg_first + j;
@@ -2073,9 +2089,11 @@ int rt_set_scene(rt_context* c, const rt_scene* in) {
   }
   s.kinds.assign(kind.begin(), kind.begin() + s.nobj);  // top-level objects (test counts)
   {
-    // Acceleration buffer: [BVH nodes | leaf objects] | planes.
+    // Acceleration buffer: [BVH nodes | leaf objects] | unbounded objects
+    // (planes, composites, never-culled objects).
     std::vector<int> bounded, planes;
-    for (int i = 0; i < s.nobj; i++) (kind[i] == RT_PLANE || kind[i] == RT_CSG ? planes : bounded).push_back(i);
+    for (int i = 0; i < s.nobj; i++)
+      (kind[i] == RT_PLANE || kind[i] == RT_CSG || !std::isfinite(brad[i]) ? planes : bounded).push_back(i);
     BvhBuild b;
     if ((c->accel & RT_ACCEL_BVH) && (int)bounded.size() >= BVH_MIN) {
       b.c = &bcen;

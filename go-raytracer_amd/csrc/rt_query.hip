@@ -305,7 +305,7 @@ struct SceneSearch {
         list_obj(i);
       }
     } else {
-      for (int p = 0; p < Q.nplanes; p++) {  // unbounded objects: planes, composites
+      for (int p = 0; p < Q.nplanes; p++) {  // unbounded objects: planes, composites, never-culled objects
         if (occl && !wave_any(open)) break;
         list_obj(__builtin_amdgcn_readfirstlane(Q.planes[p]));
       }

@@ -664,12 +664,22 @@ __device__ __forceinline__ bool wave_any(bool b) { return __builtin_amdgcn_ballo
 __device__ __forceinline__ uint64_t popc_ballot(bool b) { return (uint64_t)__popcll(wave_ballot(b)); }
 
 // Conservative FP32 test: can the segment o + t*d, 0 < t < tmax (d ~ unit)
-// come within the padded bounding sphere (centre c, radius^2 r2)? The exact
-// FP64 test can only report a hit whose point lies inside the object's
-// bounding sphere (to ~1e-12 relative); the host pads the radius by 0.01%
-// plus 1e-4*(1+|c|+|L|) and tmax carries 1e-4 relative slack, ~100x FP32
-// rounding at scene scales, so `false` proves the exact test misses (or, for
-// closestHit, cannot beat the current best).
+// come within the padded bounding sphere (centre c, radius^2 r2)? The bar is
+// the exact FP64 test's own answer, not geometry. Where that test is accurate
+// it can only report a hit whose point lies inside the object's bounding
+// sphere (to ~1e-12 relative); the host pads the radius by 0.01% plus
+// 1e-4*(1+|c|+|L|) and tmax carries 1e-4 relative slack, ~100x FP32 rounding
+// at scene scales, so `false` proves the exact test misses (or, for
+// closestHit, cannot beat the current best). It is not accurate everywhere:
+//  - From D units away the quadric discriminant errs by ~2^-53 D^2, and the
+//    test reports hits of rays that pass up to 2.7e-8 D beside the object, at
+//    a t up to 2.7e-8 D off it (measured from the oracle alone,
+//    tests/test_cull_limits_ref.py). ray_slack's 1e-5 (1 + |o|) covers that
+//    for the ray's own origin; a shifted origin adds RT_FAR_ERR (far_shift).
+//  - Under an ill-conditioned transform (|o2w|_F |w2o|_F from 1e8) the
+//    cofactor inverse and the object-space quadratic no longer describe the
+//    object the sphere encloses. The host gives an object above 1e6 an
+//    infinite radius and lists it with the unbounded ones: never culled.
 struct F3 {
   float x, y, z;
 };
@@ -789,18 +799,33 @@ __device__ __forceinline__ void bvh_next(WaveStack& st, int& sp, int lane, bool 
 // objects, o' = o + t0 d, and its bounds become tmax - t0; a lane whose ray
 // misses that box takes no part. Objects lie in the box, so every cull that
 // could pass for o passes for o' (both conservative); the exact tests still
-// use the reference's ray, so hits and counters do not change.
+// use the reference's ray, so hits and counters do not change. They also keep
+// that ray's error: from D units away they answer for rays that pass up to
+// 2.7e-8 D beside the object and return a t as far off it (see may_hit).
+// RT_FAR_ERR = 2^-22 is the next power of two above 8 x that measurement. D is
+// at most |o|_1 + |c|_1 + r; the object's share RT_FAR_ERR (|c|_1 + r) is
+// below 1 % of the host's padding 1e-4 (1 + |c| + |L|), and the origin's share
+// e = RT_FAR_ERR |o|_1 comes from the lane's own slack 1e-5 (1 + |o|_1) (times
+// 1.001 for its FP32 roundings). e enters twice: the box is widened by it, so
+// a ray that misses the objects' box by less than the error still takes part
+// and no reported t lies before t0; and the slack at o' keeps it. Without e a
+// closest-hit query from 1e7 units and the shadow rays of a ground hit 1e6
+// units out differed from the reference (tests/test_gpu_cull_limits.py).
+#define RT_FAR_ERR 2.384185791015625e-07f
+__device__ __forceinline__ float far_err(float slack) { return slack * (RT_FAR_ERR * 1.001e5f); }
 __device__ __forceinline__ void far_shift(bool& act, const Ray& r, const double* lo, const double* hi, F3& of,
                                           float& slack, double& t0) {
   if (!RT_FAR_SHIFT || !wave_any(act && slack > 1e-3f)) return;
   if (act && slack > 1e-3f) {
     const double o[3] = {r.o.x, r.o.y, r.o.z}, d[3] = {r.d.x, r.d.y, r.d.z};
+    const float ef = far_err(slack);
+    const double e = (double)ef;
     double tn = 0.0, tf = __builtin_inf();
 #pragma unroll
     for (int a = 0; a < 3; a++) {
       // d = 0: +-inf (inside the slab: no bound; outside: empty); 0/0 = NaN is
       // ignored by fmin/fmax
-      const double ta = (lo[a] - o[a]) / d[a], tb = (hi[a] - o[a]) / d[a];
+      const double ta = (lo[a] - e - o[a]) / d[a], tb = (hi[a] + e - o[a]) / d[a];
       tn = __builtin_fmax(tn, __builtin_fmin(ta, tb));
       tf = __builtin_fmin(tf, __builtin_fmax(ta, tb));
     }
@@ -810,7 +835,7 @@ __device__ __forceinline__ void far_shift(bool& act, const Ray& r, const double*
       t0 = tn * (1.0 - 1e-9);
       const d3 os = add(r.o, scale(r.d, t0));
       of = f3(os);
-      slack = ray_slack(of);
+      slack = ray_slack(of) + ef;
     }
   }
 }
@@ -1159,7 +1184,7 @@ __device__ __forceinline__ bool csg_hit(DP geo, IP kinds, IP code, int nobj,
       if (t0 > 0.0) {
         tc = t0;
         of = f3(add(r.o, scale(r.d, t0)));
-        slack = ray_slack(of);
+        slack = ray_slack(of) + far_err(slack);  // (the leaves' exact tests keep the far origin: see far_shift)
       }
     }
   }
@@ -2951,7 +2976,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
         }
 #endif
       } else {
-        for (int p = 0; p < P.nplanes; p++) {  // unbounded objects: planes, unbounded CSG
+        for (int p = 0; p < P.nplanes; p++) {  // unbounded objects: planes, composites, never-culled objects
           const int i = P.planes[p];
           trace_obj(i, S.kind[i], S.geo + (size_t)i * GEO, tr);
         }
