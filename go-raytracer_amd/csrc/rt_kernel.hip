@@ -530,7 +530,7 @@ struct SpecKey {
 // Launch configuration of one (kernel, fixed LDS, frames) combination.
 struct LaunchPlan {
   const void* fn = nullptr;
-  int shmem_fixed = -1, frames = 0, per_cu = 0, lds_levels = 0, lds_full = 0;
+  int shmem_fixed = -1, frames = 0, per_cu = 0, lds_levels = 0;
 };
 
 struct rt_context {
@@ -2413,29 +2413,20 @@ static int launch(rt_context* c, int y0, int y1, int trow0, int stride, int ntro
   // The frame cores of the shallowest recursion levels live in the LDS that
   // is left over at this occupancy (never lowering it); deeper levels stay in
   // the HBM frame stack. RT_LDS_LEVELS=n caps the count (experiments).
-  // RT_LDS_FULL=n (experiments) also moves the other frame fields (first
-  // child's colour, pending refraction ray) of the first n levels to LDS.
   const int level_bytes = WAVES_PER_WG * CORE * 64 * (int)sizeof(double);
-  const int ext_bytes = WAVES_PER_WG * EXT_ROWS * 64 * (int)sizeof(double);
-  int lds_levels = plan_hit ? pl.lds_levels : 0, lds_full = plan_hit ? pl.lds_full : 0;
+  int lds_levels = plan_hit ? pl.lds_levels : 0;
   if (!plan_hit && c->lds_per_cu > 0 && c->lds_per_block > 0) {
     const int avail = std::min(c->lds_per_block, c->lds_per_cu / std::min(per_cu, 8)) - shmem;
-    if (const char* e = rt_getenv("RT_LDS_FULL")) lds_full = std::max(0, std::min(frames, atoi(e)));
-    while (lds_full > 0 && lds_full * (ext_bytes + level_bytes) > avail) lds_full--;
-    lds_levels = std::max(lds_full, std::min(frames, (avail - lds_full * ext_bytes) / level_bytes));
-    if (const char* e = rt_getenv("RT_LDS_LEVELS")) lds_levels = std::max(lds_full, std::min(lds_levels, atoi(e)));
-    while (lds_levels > 0 && occupancy(shmem + lds_levels * level_bytes + lds_full * ext_bytes) < per_cu) {
-      lds_levels--;
-      lds_full = std::min(lds_full, lds_levels);
-    }
+    lds_levels = std::max(0, std::min(frames, avail / level_bytes));
+    if (const char* e = rt_getenv("RT_LDS_LEVELS")) lds_levels = std::max(0, std::min(lds_levels, atoi(e)));
+    while (lds_levels > 0 && occupancy(shmem + lds_levels * level_bytes) < per_cu) lds_levels--;
   }
-  if (!plan_hit) pl = LaunchPlan{plan_fn, shmem, frames, per_cu, lds_levels, lds_full};
-  const int ext_off = shmem + lds_levels * level_bytes;
-  shmem = ext_off + lds_full * ext_bytes;
+  if (!plan_hit) pl = LaunchPlan{plan_fn, shmem, frames, per_cu, lds_levels};
+  shmem += lds_levels * level_bytes;
   static const bool dbg = rt_getenv("RT_DEBUG_LAUNCH") != nullptr;
   if (dbg)
-    fprintf(stderr, "[launch] blocks/CU %d, LDS/block %d B (fixed %d, frame cores %d levels, full frames %d levels), frames %d\n",
-            per_cu, shmem, frames_off, lds_levels, lds_full, frames);
+    fprintf(stderr, "[launch] blocks/CU %d, LDS/block %d B (fixed %d, frame cores %d levels), frames %d\n", per_cu, shmem,
+            frames_off, lds_levels, frames);
   const int grid = c->cus * std::min(per_cu, 8);
   c->last_waves = grid * WAVES_PER_WG;
   c->launches++;
@@ -2469,9 +2460,7 @@ static int launch(rt_context* c, int y0, int y1, int trow0, int stride, int ntro
   std::memset(&P, 0, sizeof P);
   P.lds_frames_off = frames_off;
   P.lds_levels = lds_levels;
-  P.lds_full = lds_full;
   P.stream_off = stream_off;
-  P.lds_ext_off = ext_off;
   P.qmask_off = qmask_off;
   P.jump_off = jump_off;
   P.board_off = board_off;

@@ -136,7 +136,7 @@ enum { GEO = 16, SHD = 32, MAT = 16, LGT = 16, OMAT = 8, GLOB = 16 };
 // -- the reflection child's colour in its first three rows (a glass frame keeps
 // 6 rows, not 9: a third fewer dirty lines written back per frame). The CORE
 // fields (Lw, kr, packed) of the first P.lds_levels levels live in LDS
-// instead, ext of the first P.lds_full levels too; the rest live in HBM.
+// instead; everything else lives in HBM.
 enum { FRAME_FIELDS = 15, CORE = 5, EXT_ROWS = 6, FR_EXT = 3, FR_COL = 11, FR_REFL = 14 };
 enum { CHUNK = 64, TILE = 8, WG = 256, WAVES_PER_WG = WG / 64 };
 // Work queue: pixels per dequeue -- one 8x8 tile, or with pixel quads a 4x4
@@ -196,8 +196,6 @@ __device__ __forceinline__ int est_y(int pts, unsigned int k) { return pts == 1 
 struct Params {
   int lds_frames_off;  // byte offset of the LDS frame cores in dynamic LDS
   int lds_levels;      // recursion levels whose frame core lives in LDS (host: LDS left at full occupancy)
-  int lds_full;        // recursion levels whose other frame fields (3..11) live in LDS too
-  int lds_ext_off;     // byte offset of those fields in dynamic LDS
   int stream_off;      // byte offset of the per-wave object-record stream buffers (global linear scenes)
   int qmask_off;       // byte offset of the workgroup's drained-head mask in LDS
   int jump_off;        // byte offset of the LDS copy of the sample-0 jump rows (serial samples)
@@ -323,6 +321,13 @@ __device__ __forceinline__ d3 axis_d(const double* a, d3 d) { return mk(a[0] * d
 typedef const __attribute__((address_space(4))) double* cdptr;
 typedef const __attribute__((address_space(4))) float* cfptr;
 typedef const __attribute__((address_space(4))) int* ciptr;
+// The per-lane frame stack, typed by where a level lives: LDS frame cores
+// and HBM frames. Two distinct address spaces keep the compiler from merging
+// the two sides of a `level < lds_levels` choice into one generic pointer
+// (a FLAT access, which counts on vmcnt and lgkmcnt both and needs a 64-bit
+// address select per field); LDS addresses are 32-bit arithmetic.
+typedef __attribute__((address_space(3))) double* ldptr;
+typedef __attribute__((address_space(1))) double* gdptr;
 // the FP32 words of a double record, in the record's address space
 __device__ __forceinline__ const float* as_f(const double* p) { return reinterpret_cast<const float*>(p); }
 __device__ __forceinline__ cfptr as_f(cdptr p) { return (cfptr)p; }
@@ -1413,18 +1418,28 @@ __device__ __forceinline__ uint64_t stamp() {
 
 // Frame stack: lane-interleaved so that one field of one frame is a
 // contiguous 512-B row for the wave.
-__device__ __forceinline__ double* frame_ptr(double* base, int frame) { return base + (size_t)frame * FRAME_FIELDS * 64; }
-__device__ __forceinline__ void st3(double* f, int field, d3 v) {
-  f[(field + 0) * 64] = v.x;
-  f[(field + 1) * 64] = v.y;
-  f[(field + 2) * 64] = v.z;
+// A frame is addressed by its middle row (FRAME_MID), so that every field is
+// within the signed 13-bit immediate offset of a global access (rows are
+// 512 B apart: -3584 .. +3584 B) and a frame needs one address. `base` is the
+// wave's stack (wave-uniform), `lane8` the lane's byte offset in row
+// FRAME_MID: the per-lane part of the address is one 32-bit multiply-add,
+// which the access takes next to the scalar base.
+enum { FRAME_MID = FRAME_FIELDS / 2, FRAME_BYTES = FRAME_FIELDS * 64 * 8 };
+__device__ __forceinline__ gdptr frame_ptr(gdptr base, uint32_t lane8, int frame) {
+  typedef __attribute__((address_space(1))) char* gbptr;
+  return (gdptr)((gbptr)base + (__umul24((uint32_t)frame, (uint32_t)FRAME_BYTES) + lane8));
 }
-__device__ __forceinline__ d3 ld3(const double* f, int field) {
-  return mk(f[(field + 0) * 64], f[(field + 1) * 64], f[(field + 2) * 64]);
+__device__ __forceinline__ __attribute__((address_space(1))) double& fr(gdptr f, int field) { return f[(field - FRAME_MID) * 64]; }
+__device__ __forceinline__ void st3(gdptr f, int field, d3 v) {
+  fr(f, field + 0) = v.x;
+  fr(f, field + 1) = v.y;
+  fr(f, field + 2) = v.z;
 }
+__device__ __forceinline__ d3 ld3(gdptr f, int field) { return mk(fr(f, field + 0), fr(f, field + 1), fr(f, field + 2)); }
 
 // CORE field c (0..2 Lw, 3 kr, 4 packed) -> global field index.
-__device__ __forceinline__ int core_gfield(int c) { return c < 3 ? c : (c == 3 ? 9 : 10); }
+__device__ __forceinline__ constexpr int core_gfield(int c) { return c < 3 ? c : (c == 3 ? 9 : 10); }
+enum { CF_LW = 0, CF_KR = 3, CF_PACKED = 4 };
 
 // Frame flags (packed with the material index): packed = material << PK_MAT |
 // board slot << PK_SLOT | flags. FL_FORKED: the pending refraction child was
@@ -1917,28 +1932,61 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
 
   const int lane = (int)(threadIdx.x & 63);
   const int wslot = (int)(blockIdx.x * WAVES_PER_WG + (threadIdx.x >> 6));
-  double* stk = P.stack + (size_t)wslot * ((size_t)P.frames * FRAME_FIELDS * 64) + lane;
+  // the wave's HBM frame stack (wave-uniform: a scalar base) and its LDS frame cores
+  const gdptr stk = (gdptr)P.stack + (size_t)__builtin_amdgcn_readfirstlane(wslot) * ((size_t)P.frames * FRAME_FIELDS * 64);
+  // (opaque: folded back into the immediates, they no longer all fit)
+  uint32_t lane8 = (uint32_t)lane * 8u + FRAME_MID * 512u;
+  asm volatile("" : "+v"(lane8));
+  auto frame = [&](int level) -> gdptr { return frame_ptr(stk, lane8, level); };
   const int lds_lv = P.lds_levels;
-  double* lfr = reinterpret_cast<double*>(smem + P.lds_frames_off) +
-                (size_t)(threadIdx.x >> 6) * (lds_lv * CORE * 64) + lane;
-  // frame core accessors: level < lds_levels in LDS, deeper in HBM
-  auto core_ld = [&](int level, int c) -> double {
-    if (level < lds_lv) return lfr[(level * CORE + c) * 64];
-    return frame_ptr(stk, level)[core_gfield(c) * 64];
+  typedef __attribute__((address_space(3))) char* lbptr;
+  const lbptr lfr = (lbptr)(smem + P.lds_frames_off) + ((int)(threadIdx.x >> 6) * (lds_lv * CORE * 512) + lane * 8);
+  auto lcore = [&](int level) -> ldptr { return (ldptr)(lfr + __umul24((uint32_t)level, (uint32_t)(CORE * 512))); };
+  // Frame core accessors: level < lds_levels in LDS, deeper in HBM. The level
+  // is per lane, so a wave may run both sides. A whole core moves with one
+  // decision and one address per side, the fields at immediate offsets from
+  // it (LDS: 512 B apart, the st64-paired DS forms; HBM: core_gfield).
+  auto core_load = [&](int level, long long& packed, d3& lw, double& kr) {
+    if (level < lds_lv) {
+      const ldptr p = lcore(level);
+      lw = mk(p[(CF_LW + 0) * 64], p[(CF_LW + 1) * 64], p[(CF_LW + 2) * 64]);
+      kr = p[CF_KR * 64];
+      packed = __double_as_longlong(p[CF_PACKED * 64]);
+    } else {
+      const gdptr f = frame(level);
+      lw = ld3(f, core_gfield(CF_LW));
+      kr = fr(f, core_gfield(CF_KR));
+      packed = __double_as_longlong(fr(f, core_gfield(CF_PACKED)));
+    }
   };
-  // ext rows of `level` (pending refraction ray, then the first child's
-  // colour; LDS for level < lds_full).
-  const int lds_full = P.lds_full;
-  double* lext = reinterpret_cast<double*>(smem + P.lds_ext_off) + (size_t)(threadIdx.x >> 6) * (lds_full * EXT_ROWS * 64) + lane;
-  auto ext = [&](int level) -> double* {
-    return level < lds_full ? lext + (size_t)level * EXT_ROWS * 64 : frame_ptr(stk, level) + FR_EXT * 64;
+  auto core_store = [&](int level, long long packed, d3 lw, double kr) {
+    if (level < lds_lv) {
+      const ldptr p = lcore(level);
+      p[(CF_LW + 0) * 64] = lw.x;
+      p[(CF_LW + 1) * 64] = lw.y;
+      p[(CF_LW + 2) * 64] = lw.z;
+      p[CF_KR * 64] = kr;
+      p[CF_PACKED * 64] = __longlong_as_double(packed);
+    } else {
+      const gdptr f = frame(level);
+      st3(f, core_gfield(CF_LW), lw);
+      fr(f, core_gfield(CF_KR)) = kr;
+      fr(f, core_gfield(CF_PACKED)) = __longlong_as_double(packed);
+    }
   };
-  auto core_st = [&](int level, int c, double v) {
+  // `packed` alone (the FL_STAGE write-back, wait_slot, the sharing paths)
+  auto packed_ld = [&](int level) -> long long {
+    if (level < lds_lv) return __double_as_longlong(lcore(level)[CF_PACKED * 64]);
+    return __double_as_longlong(fr(frame(level), core_gfield(CF_PACKED)));
+  };
+  auto packed_st = [&](int level, long long packed) {
     if (level < lds_lv)
-      lfr[(level * CORE + c) * 64] = v;
+      lcore(level)[CF_PACKED * 64] = __longlong_as_double(packed);
     else
-      frame_ptr(stk, level)[core_gfield(c) * 64] = v;
+      fr(frame(level), core_gfield(CF_PACKED)) = __longlong_as_double(packed);
   };
+  // (the other fields -- FR_EXT: the pending refraction ray, then the first
+  // child's colour; FR_COL, FR_REFL -- are always in HBM: frame(level))
   // Per-lane material record written by the surface VM (same layout as mats).
   double* vmrec;
   if constexpr (LDS)
@@ -2104,7 +2152,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
   // `sample` (at sp == 0), else the posted refraction child of frame sp - 1.
   auto wait_slot = [&]() -> int {
     if (RT_SHARE == 1 && !QD && sp == 0) return lw_fork(Bd->lw[threadIdx.x], sample);
-    return PK_SLOT_OF(__double_as_longlong(core_ld(sp - 1, 4)));
+    return PK_SLOT_OF(packed_ld(sp - 1));
   };
   // Serial samples: account sample `sample` onwards after the lane finished
   // the one before -- run it (own), take a helper's colour, reclaim a posted
@@ -2184,12 +2232,9 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
           }
           have_res = false;
         } else {
-          double* f = frame_ptr(stk, sp - 1);
-          long long packed;
-          if (pf_valid)
-            packed = pf_packed;
-          else
-            packed = __double_as_longlong(core_ld(sp - 1, 4));
+          const gdptr f = frame(sp - 1);
+          if (!pf_valid) core_load(sp - 1, pf_packed, pf_lw, pf_kr);
+          const long long packed = pf_packed;
           int fl = (int)(packed & 0xff);
           if (RT_SHARE && __builtin_expect((fl & FL_TASK) != 0, 0)) {  // a claimed subtree is done: hand its colour to the owner
             if constexpr (RT_SHARE == 2)
@@ -2202,10 +2247,9 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
           } else if ((fl & FL_HASR) && (fl & FL_HAST) && !(fl & FL_STAGE)) {
             // reflection child done; trace the pending refraction child.
             // Its colour takes the pending ray's rows once the ray is read.
-            double* e = ext(sp - 1);
             const d3 first = res;
             bool here = true;
-            core_st(sp - 1, 4, __longlong_as_double(packed | FL_STAGE));
+            packed_st(sp - 1, packed | FL_STAGE);
             if (RT_SHARE && __builtin_expect((fl & FL_FORKED) != 0, 0)) {
               const int q = PK_SLOT_OF(packed);
               if (RT_SHARE == 2 ? gs_reclaim(P.gboard, q) : board_reclaim(Bd, q)) {  // nobody took it: trace it here
@@ -2222,37 +2266,30 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
               }
             }
             if (here) {
-              ray.o = ld3(e, 0);
-              ray.d = ld3(e, 3);
+              ray.o = ld3(f, FR_EXT);
+              ray.d = ld3(f, FR_EXT + 3);
               state = S_TRACE;
               have_res = false;
             }
-            st3(e, 0, first);
+            st3(f, FR_EXT, first);
           } else {
             const double* FM = S.mats + (size_t)(packed >> PK_MAT) * MAT;
             d3 R = mk(0, 0, 0), Tr = mk(0, 0, 0);
             if ((fl & FL_HASR) && (fl & FL_HAST)) {
-              R = ld3(ext(sp - 1), 0);
+              R = ld3(f, FR_EXT);
               Tr = res;
             } else if (fl & FL_HASR) {
               R = res;
             } else {
               Tr = res;
             }
-            d3 lw;
-            double kr;
-            if (pf_valid) {
-              lw = pf_lw;
-              kr = pf_kr;
-            } else {
-              lw = mk(core_ld(sp - 1, 0), core_ld(sp - 1, 1), core_ld(sp - 1, 2));
-              kr = core_ld(sp - 1, 3);
-            }
+            const d3 lw = pf_lw;
+            const double kr = pf_kr;
             d3 fcol;
             double frefl;
             if (spec_feat(SF_VM) && (fl & FL_VMMAT)) {
               fcol = ld3(f, FR_COL);
-              frefl = f[FR_REFL * 64];
+              frefl = fr(f, FR_REFL);
             } else {
               fcol = mk(FM[0], FM[1], FM[2]);
               frefl = FM[3];
@@ -2504,7 +2541,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
         // only subtrees of GS_MIN_LEVELS levels or more are worth a hand-off)
         if (busy_lane)
           for (int l = min(sp - 1, P.depth - 1 - GS_MIN_LEVELS); l >= 0; l--) {
-            const int f = (int)(__double_as_longlong(core_ld(l, 4)) & 0xff);
+            const int f = (int)(packed_ld(l) & 0xff);
             if (f & FL_TASK) break;
             if ((f & (FL_HASR | FL_HAST | FL_STAGE | FL_FORKED)) == (FL_HASR | FL_HAST)) L = l;
           }
@@ -2519,8 +2556,8 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
             SHDIAG(SH_POST_T);
             q = (wslot * 64 + lane) * P.frames + L;
             uint64_t* r = gs_slot(P.gboard, q);
-            const double* e = ext(L);
-            const d3 o = ld3(e, 0), dd = ld3(e, 3);
+            const gdptr e = frame(L);
+            const d3 o = ld3(e, FR_EXT), dd = ld3(e, FR_EXT + 3);
             gs_st(r + 0, (uint64_t)__double_as_longlong(o.x));
             gs_st(r + 1, (uint64_t)__double_as_longlong(o.y));
             gs_st(r + 2, (uint64_t)__double_as_longlong(o.z));
@@ -2530,8 +2567,8 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
             gs_st(r + 6, (uint64_t)(L + 1));
             gs_drain();
             gs_st(r + 7, GS_POSTED);
-            const long long pk = __double_as_longlong(core_ld(L, 4));
-            core_st(L, 4, __longlong_as_double(pk | FL_FORKED | ((long long)q << PK_SLOT)));
+            const long long pk = packed_ld(L);
+            packed_st(L, pk | FL_FORKED | ((long long)q << PK_SLOT));
           }
           gs_drain();  // every posted slot's state has landed before its ticket
           uint64_t t0 = 0;
@@ -2612,7 +2649,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
                 const int m0 = (int)gs_ld(r + 6);
                 // a sentinel below the subtree (its colour goes to slot q); the
                 // subtree runs at its own absolute levels
-                core_st(m0 - 1, 4, __longlong_as_double((long long)FL_TASK | ((long long)q << PK_SLOT)));
+                packed_st(m0 - 1, (long long)FL_TASK | ((long long)q << PK_SLOT));
                 sp = m0;
                 state = S_TRACE;
               }
@@ -2689,7 +2726,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
         int L = -1;
         if (busy_lane && !cs)
           for (int l = sp - 1; l >= 0; l--) {
-            const int f = (int)(__double_as_longlong(core_ld(l, 4)) & 0xff);
+            const int f = (int)(packed_ld(l) & 0xff);
             if (f & FL_TASK) break;
             if ((f & (FL_HASR | FL_HAST | FL_STAGE | FL_FORKED)) == (FL_HASR | FL_HAST)) L = l;
           }
@@ -2714,8 +2751,8 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
                 Bd->lw[threadIdx.x] = (w & ~7u & ~(63u << sh)) | (uint32_t)k | ((uint32_t)q << sh);
               } else {  // the pending refraction child of frame L, traced at level L + 1
                 SHDIAG(SH_POST_T);
-                const double* e = ext(L);
-                const d3 o = ld3(e, 0), dd = ld3(e, 3);
+                const gdptr e = frame(L);
+                const d3 o = ld3(e, FR_EXT), dd = ld3(e, FR_EXT + 3);
                 Bd->ray[q][0] = o.x;
                 Bd->ray[q][1] = o.y;
                 Bd->ray[q][2] = o.z;
@@ -2724,8 +2761,8 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
                 Bd->ray[q][5] = dd.z;
                 Bd->meta[q][0] = L + 1;
                 Bd->meta[q][1] = 0;
-                const long long pk = __double_as_longlong(core_ld(L, 4));
-                core_st(L, 4, __longlong_as_double(pk | FL_FORKED | ((long long)q << PK_SLOT)));
+                const long long pk = packed_ld(L);
+                packed_st(L, pk | FL_FORKED | ((long long)q << PK_SLOT));
               }
             }
             if (lane == 0) {
@@ -2766,7 +2803,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
             } else {  // a refraction subtree at level m0 >= 1, under a sentinel frame
               ray.o = mk(Bd->ray[q][0], Bd->ray[q][1], Bd->ray[q][2]);
               ray.d = mk(Bd->ray[q][3], Bd->ray[q][4], Bd->ray[q][5]);
-              core_st(m0 - 1, 4, __longlong_as_double((long long)FL_TASK | ((long long)q << PK_SLOT)));
+              packed_st(m0 - 1, (long long)FL_TASK | ((long long)q << PK_SLOT));
               Bd->lw[threadIdx.x] = 0u;
               sp = m0;
             }
@@ -2840,9 +2877,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
       double pf_kr = 0.0;
       if (tr && sp > 0) {
         pf = true;
-        pf_packed = __double_as_longlong(core_ld(sp - 1, 4));
-        pf_lw = mk(core_ld(sp - 1, 0), core_ld(sp - 1, 1), core_ld(sp - 1, 2));
-        pf_kr = core_ld(sp - 1, 3);
+        core_load(sp - 1, pf_packed, pf_lw, pf_kr);
       }
       bool found = false;
       double best_t = 0.0;
@@ -3674,22 +3709,19 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
         }
         const int d = P.depth - sp;  // depth of the current ray
         if (d - 1 > 0 && (hasR || hasT)) {
-          core_st(sp, 0, lw.x);
-          core_st(sp, 1, lw.y);
-          core_st(sp, 2, lw.z);
           if (hasR && hasT) {
-            st3(ext(sp), 0, trr.o);
-            st3(ext(sp), 3, trr.d);
+            const gdptr f = frame(sp);
+            st3(f, FR_EXT, trr.o);
+            st3(f, FR_EXT + 3, trr.d);
           }
-          core_st(sp, 3, kr);
           if (spec_feat(SF_VM) && mat < 0) {  // the VM record is per lane: keep what the combine needs
-            double* f = frame_ptr(stk, sp);
+            const gdptr f = frame(sp);
             st3(f, FR_COL, col);
-            f[FR_REFL * 64] = refl;
+            fr(f, FR_REFL) = refl;
           }
           long long packed = ((long long)(mat < 0 ? 0 : mat) << PK_MAT) | (mat < 0 ? FL_VMMAT : 0) |
                              (tmode ? FL_TMODE : 0) | (hasR ? FL_HASR : 0) | (hasT ? FL_HAST : 0);
-          core_st(sp, 4, __longlong_as_double(packed));
+          core_store(sp, packed, lw, kr);
           sp++;
           ray = hasR ? rr : trr;
           state = S_TRACE;
