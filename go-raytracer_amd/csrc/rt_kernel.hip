@@ -2362,10 +2362,6 @@ static int launch(rt_context* c, int y0, int y1, int trow0, int stride, int ntro
   const int vm_off = lds ? s.blob_bytes : 0;
   const int stack_off = vm_off + ((lds && s.num_programs) ? WG * MAT * (int)sizeof(double) : 0);
   const int cnt_off = stack_off + (s.use_bvh ? WAVES_PER_WG * BVH_STACK * 12 : 0);
-  const int qmask_off = cnt_off + CNT_BYTES;
-  // per-wave object-record stream buffers (global linear scenes, rt_render.h stream_objects)
-  const int jump_off = qmask_off + 16;  // after the drained-head mask: the sample-0 jump rows
-  const int board_off = jump_off + 20 * 4 * (int)sizeof(uint64_t);  // work-sharing board (RT_SHARE)
   const uint64_t launch_pixels = (uint64_t)s.width * (uint64_t)(stride > 0 ? ntrows * TILE : y1 - y0);
   const int sch =
       est ? (int)SCH_SERIAL : pick_schedule(c->sched, s, launch_pixels, c->cus, c->inflight, c->spec_fn != nullptr);
@@ -2380,6 +2376,15 @@ static int launch(rt_context* c, int y0, int y1, int trow0, int stride, int ntro
     int rc = spec_for(c, sch, share_m, &spec);
     if (rc != RT_OK) return rc;
   }
+  // The counter area is smaller in the kernels that keep the shadow-test
+  // tallies packed in registers (rt_render.h SC_BUILD: compile-time objects
+  // and lights; a key with objects has neither BVH nor CSG). Every variant of
+  // a scene's key shares its objects and lights.
+  const bool sc_packed = spec && c->spec_key.nobj > 0 && c->spec_key.nlights > 0;
+  const int qmask_off = cnt_off + cnt_bytes(sc_packed);
+  const int jump_off = qmask_off + 16;  // after the drained-head mask: the sample-0 jump rows
+  const int board_off = jump_off + 20 * 4 * (int)sizeof(uint64_t);  // work-sharing board (RT_SHARE)
+  // per-wave object-record stream buffers (global linear scenes, rt_render.h stream_objects)
   // (the brute-force specialised kernel, RT_CULL=0, reads records with scalar
   // loads instead: no stream buffers; tuning builds with RT_SPEC_EXTRA_FLAGS
   // keep the buffers: they may select the LDS stream)

@@ -56,6 +56,8 @@
 #ifndef RT_GS_HELPERS
 #define RT_GS_HELPERS 16  // drained waves that stay to help (device-wide); the others leave at once
 #endif
+// (tests/test_gpu_shadow_counts.py likewise: RT_SC_FLUSH, SHADE passes between
+// flushes of the packed shadow-test tallies; default at SC_BUILD below)
 // Macros so that a bad value fails the compile (tests/test_gpu_render_api.py
 // forces a compile error through RT_SHADE_NUM):
 #ifndef RT_SHADE_NUM
@@ -256,10 +258,73 @@ struct Params {
 // SGPR spilling (C2 +33% time, C3 +7%).
 // Unit events (traced rays, shaded hits, surface errors) are counted per wave
 // (lane 0 adds the ballot's popcount); per-kind shadow-test tallies per lane.
-// LDS: [NUNIT][WAVES_PER_WG] then, CNT_KIND_OFF bytes in, [RT_NUM_KINDS][WG].
-enum { CNT_TRACED = 0, CNT_SHADED = 1, CNT_SURFERR = 2, NUNIT = 3, CNT_KIND_OFF = 128,
-       CNT_BYTES = CNT_KIND_OFF + RT_NUM_KINDS * WG * 8 };
+// LDS: [NUNIT][WAVES_PER_WG] then, CNT_KIND_OFF bytes in, [RT_NUM_KINDS][WG]
+// -- or, in the kernels that keep the tallies packed in registers (SC_BUILD,
+// below), [RT_NUM_KINDS][WAVES_PER_WG] per-wave totals.
+enum { CNT_TRACED = 0, CNT_SHADED = 1, CNT_SURFERR = 2, NUNIT = 3, CNT_KIND_OFF = 128 };
+// Bytes of the counter area: the one rule for the host's LDS layout
+// (rt_kernel.hip launch) and for the kernel.
+__host__ __device__ constexpr int cnt_bytes(bool packed) {
+  return CNT_KIND_OFF + RT_NUM_KINDS * (packed ? WAVES_PER_WG : WG) * 8;
+}
 enum { PREF = 8 };  // u32 per prefix-count entry (RT_NUM_KINDS used, 16-B aligned)
+
+// Packed shadow-test tallies (small linear scenes with compile-time kinds and
+// light count, no BVH or CSG). inShadow's test count per kind is a function of
+// the first occluder's index and the hit's own index alone, and both meet
+// compile-time object indices in the unrolled shadow loop, so the prefix
+// counts are literals: SC.pk[w][s] holds, in one 8-bit field per kind present,
+// the objects of that kind with index < s (<= 8). A SHADE pass sums one such
+// word per light (a field stays <= lights * objects <= 64), widens the sum
+// into 16-bit fields of a per-lane accumulator, and the wave adds its lanes'
+// accumulators into per-wave u64 totals in LDS every SC_FLUSH passes and when
+// it leaves the main loop. No prefix-table read, no S.kind read, no per-pass
+// LDS atomics, and no [RT_NUM_KINDS][WG] u64 in LDS.
+#if defined(RT_SPEC_NOBJ) && defined(RT_SPEC_NLIGHTS)
+constexpr bool SC_BUILD = true;
+static_assert(RT_SPEC_NOBJ >= 1 && RT_SPEC_NOBJ <= 8 && RT_SPEC_NLIGHTS >= 1 && RT_SPEC_NLIGHTS <= 8,
+              "packed tallies: a pass's 8-bit fields hold at most lights * objects <= 64");
+// Passes between flushes: a 16-bit field gains at most lights * objects per
+// pass (-DRT_SC_FLUSH=n through RT_SPEC_EXTRA_FLAGS: tests force flushes on
+// tiny frames).
+#ifndef RT_SC_FLUSH
+#define RT_SC_FLUSH (65535 / (RT_SPEC_NLIGHTS * RT_SPEC_NOBJ))
+#endif
+enum { SC_FLUSH = RT_SC_FLUSH, SC_NOBJ = RT_SPEC_NOBJ };
+static_assert(SC_FLUSH >= 1 && SC_FLUSH * RT_SPEC_NLIGHTS * RT_SPEC_NOBJ <= 65535, "RT_SC_FLUSH overflows a 16-bit field");
+// Four fields to a 32-bit word; five or six kinds present take two words.
+struct ScTab {
+  int field[RT_NUM_KINDS];            // field of kind k: its rank among the kinds present
+  int nfields;
+  uint32_t pk[2][RT_SPEC_NOBJ + 1];   // the prefix word w at s
+  uint32_t hit_fields;                // field of object i's kind at bits 4i..4i+2 (the hit's own, by a shift)
+};
+constexpr ScTab sc_make() {
+  ScTab t{};
+  for (int k = 0; k < RT_NUM_KINDS; k++) {
+    t.field[k] = t.nfields;
+    t.nfields += (SPEC_KMASK >> k) & 1;
+  }
+  for (int s = 0; s < RT_SPEC_NOBJ; s++) {
+    const int f = t.field[spec_kinds[s]];
+    for (int w = 0; w < 2; w++) t.pk[w][s + 1] = t.pk[w][s] + ((f >> 2) == w ? 1u << (8 * (f & 3)) : 0u);
+    t.hit_fields |= (uint32_t)f << (4 * s);
+  }
+  return t;
+}
+constexpr ScTab SC = sc_make();
+static_assert((SPEC_KMASK >> RT_NUM_KINDS) == 0 && SC.nfields >= 1 && SC.nfields <= 8, "kinds");
+enum { SC_WORDS = SC.nfields > 4 ? 2 : 1 };
+#else
+constexpr bool SC_BUILD = false;
+enum { SC_FLUSH = 1, SC_WORDS = 1, SC_NOBJ = 0 };
+struct ScTab {  // (so that the discarded branches parse)
+  int field[RT_NUM_KINDS];
+  uint32_t pk[2][1];
+  uint32_t hit_fields;
+};
+constexpr ScTab SC{};
+#endif
 // BVH node: child 0 box (lo xyz, hi xyz), child 1 box, then as int: ref 0,
 // ref 1, smallest object index under child 0, under child 1. A ref is
 // (node << 3) for an internal node, (first << 3) | count for a leaf of
@@ -1855,6 +1920,11 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
   if (threadIdx.x == 0) *qdrained = 0u;
   // per-wave unit counters: zeroed before the barrier (any wave's lane 0 adds)
   if (threadIdx.x < NUNIT * WAVES_PER_WG) reinterpret_cast<unsigned long long*>(smem + P.cnt_off)[threadIdx.x] = 0ull;
+  // packed shadow-test tallies (SC_BUILD): the per-wave totals, likewise
+  constexpr bool SCP = SC_BUILD && !BVH && !CSG;
+  if constexpr (SCP)
+    if (threadIdx.x < RT_NUM_KINDS * WAVES_PER_WG)
+      reinterpret_cast<unsigned long long*>(smem + P.cnt_off + CNT_KIND_OFF)[threadIdx.x] = 0ull;
   Board* Bd = reinterpret_cast<Board*>(smem + P.board_off);
   if constexpr (RT_SHARE == 1) {
     if (threadIdx.x == 0) {
@@ -2078,7 +2148,27 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
   bool exhausted = false;
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(smem + P.cnt_off);
   unsigned long long* kcnt = reinterpret_cast<unsigned long long*>(smem + P.cnt_off + CNT_KIND_OFF);
-  for (int k = 0; k < RT_NUM_KINDS; k++) kcnt[k * WG + threadIdx.x] = 0;
+  if constexpr (!SCP)
+    for (int k = 0; k < RT_NUM_KINDS; k++) kcnt[k * WG + threadIdx.x] = 0;
+  // Packed tallies (SCP, see SC_BUILD): this lane's shadow tests since the
+  // wave's last flush, 16-bit fields -- word w's fields 0-1 in sc_acc[w][0],
+  // 2-3 in sc_acc[w][1] -- and the wave's SHADE passes since then
+  // (wave-uniform). A flush adds every lane's fields to the wave's totals
+  // kcnt[k * WAVES_PER_WG + wave] (one LDS atomic per kind present; rare).
+  uint32_t sc_acc[2][2] = {{0u, 0u}, {0u, 0u}};
+  int sc_passes = 0;
+  auto sc_flush = [&]() {
+#pragma unroll
+    for (int k = 0; k < RT_NUM_KINDS; k++) {
+      if (!spec_kind(k)) continue;
+      const int f = SC.field[k];
+      const uint32_t v = (sc_acc[f >> 2][(f >> 1) & 1] >> (16 * (f & 1))) & 0xffffu;
+      atomicAdd(&kcnt[k * WAVES_PER_WG + wave], (unsigned long long)v);
+    }
+#pragma unroll
+    for (int w = 0; w < SC_WORDS; w++) sc_acc[w][0] = sc_acc[w][1] = 0u;
+    sc_passes = 0;
+  };
   // The counters' LDS addresses in the BVH and CSG kernels are formed at each
   // use from a scalar base that the empty asm hides from loop-invariant
   // hoisting: hoisted, they were held in VGPRs across the main loop and
@@ -2091,7 +2181,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
     asm volatile("" : "+s"(b));
     return b;
   };
-  // shadow tests of kind k (per lane): kcnt[k * WG + threadIdx.x]
+  // shadow tests of kind k (per lane): kcnt[k * WG + threadIdx.x] (not in the SCP kernels)
   auto cnt_kind = [&](int k, uint64_t v) {
     if constexpr (CNT_REMAT) {
       uint32_t l;  // the lane number from mbcnt at the use (a hoisted one was spilled too)
@@ -3213,6 +3303,19 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
 // (the culls' origin-to-centre vectors hoisted out of the light loop
 // measured -1.5 % VALU but C3 +2..3 % from spills: not kept)
     uint32_t sc0 = 0, sc1 = 0, sc2 = 0, sc3 = 0;  // this hit's shadow tests per kind (cones: below)
+    // Packed tallies (SCP): sc_hb = one test of the hit's own kind; sc_full =
+    // a light with no occluder, SC.pk[w][nobj] less the hit itself (0 on lanes
+    // without a hit, which never find an occluder); sc_sum = this pass's sum
+    // over the lights.
+    uint32_t sc_hb[2] = {0u, 0u}, sc_full[2] = {0u, 0u}, sc_sum[2] = {0u, 0u};
+    if constexpr (SCP) {
+      const uint32_t hf = (SC.hit_fields >> (4 * (hit_i & 7))) & 7u;
+#pragma unroll
+      for (int w = 0; w < SC_WORDS; w++) {
+        sc_hb[w] = SC_WORDS == 1 ? 1u << (8 * hf) : ((hf >> 2) == (uint32_t)w ? 1u << (8 * (hf & 3u)) : 0u);
+        sc_full[w] = hit ? SC.pk[w][SC_NOBJ] - sc_hb[w] : 0u;
+      }
+    }
     // Direction and distance to a light (raytracer.go:378-380).
     auto light_dir = [&](auto lt, d3& ldir, double& dist) {
       if (spec_feat(SF_LDIR) && (int)lt[9] == RT_LIGHT_DIRECTIONAL) {  // extension: light at infinity
@@ -3390,6 +3493,9 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
       // inShadow's test count is #{i < end, i != hit} with end = first
       // occluder + 1 (or nobj); counted per kind from the prefix table below.
       int send = P.nobj;
+      // (SCP) the same count in packed fields: SC.pk[w][send] less the hit's own
+      // test where hit_i < send, set where send is
+      uint32_t spk[2] = {sc_full[0], sc_full[1]};
       if constexpr (!BVH) {
 #ifdef RT_SPEC_NOBJ
 #pragma unroll
@@ -3518,6 +3624,10 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
               if (t * rlen < dist) {
                 open = false;
                 send = i + 1;
+                if constexpr (SCP) {
+#pragma unroll
+                  for (int w = 0; w < SC_WORDS; w++) spk[w] = SC.pk[w][i + 1] - (hit_i <= i ? sc_hb[w] : 0u);
+                }
               }
             }
           }
@@ -3619,7 +3729,10 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
         open = hit && occ == 0x7fffffff;
         send = open ? P.nobj : occ + 1;
       }
-      if (hit) {
+      if constexpr (SCP) {
+#pragma unroll
+        for (int w = 0; w < SC_WORDS; w++) sc_sum[w] += spk[w];
+      } else if (hit) {
         const uint4 pe = *reinterpret_cast<const uint4*>(S.pref + (size_t)send * PREF);
         const uint32_t pe4 = S.pref[(size_t)send * PREF + 4];
         const int hk = hit_i < send ? S.kind[hit_i] : -1;
@@ -3646,7 +3759,15 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
       }
       PH_MARK(7);
     }
-    if (hit) {
+    if constexpr (SCP) {
+      // widen the pass's 8-bit fields (bytes 0-1, bytes 2-3) into the lane's 16-bit ones
+#pragma unroll
+      for (int w = 0; w < SC_WORDS; w++) {
+        sc_acc[w][0] += __builtin_amdgcn_perm(0u, sc_sum[w], 0x0c010c00u);
+        sc_acc[w][1] += __builtin_amdgcn_perm(0u, sc_sum[w], 0x0c030c02u);
+      }
+      if (++sc_passes >= SC_FLUSH) sc_flush();
+    } else if (hit) {
       if (spec_kind(0) && (P.kind_mask & 1)) cnt_kind(0, sc0);
       if (spec_kind(1) && (P.kind_mask & 2)) cnt_kind(1, sc1);
       if (spec_kind(2) && (P.kind_mask & 4)) cnt_kind(2, sc2);
@@ -3736,6 +3857,7 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
     PH_MARK(9);
   }
   flush_pixels();
+  if constexpr (SCP) sc_flush();
 
   if (lane == 0) {
 #ifdef RT_PHASE_TIMING
@@ -3783,7 +3905,8 @@ __global__ __launch_bounds__(WG, MIN_WAVES) void rt_render_kernel(const char* __
   if (!P.stats_part) {
   } else if (threadIdx.x < RT_NUM_KINDS) {
     unsigned long long sum = 0;
-    for (int j = 0; j < WG; j++) sum += kcnt[threadIdx.x * WG + j];
+    constexpr int per_kind = SCP ? WAVES_PER_WG : WG;  // per-wave totals, or per-lane tallies
+    for (int j = 0; j < per_kind; j++) sum += kcnt[threadIdx.x * per_kind + j];
     if (sum) part[ST_STESTS + threadIdx.x] += sum;
   } else if (threadIdx.x < RT_NUM_KINDS + NUNIT) {
     const int k = (int)threadIdx.x - RT_NUM_KINDS;
